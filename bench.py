@@ -15,8 +15,10 @@ configs[1] -- MuLAN-epsilon, ldm/configs/cifar10-conditioned.py (E=128, 32+2+33 
 `--global-batch G` fixes the GLOBAL batch instead (strong scaling, G/N images per GPU): BASELINE configs[2] is
 `--vdm-type mulan_velocity --global-batch 512`, configs[3] `--config ldm/configs/imagenet32.py --vdm-type mulan_velocity
 --vfe --global-batch 1024`.
-Prints ONE JSON line on rank 0 with the `roofline` (dominant kernel: the 3x3-conv implicit GEMM) and
-`cpu_baseline` (oracle port on the host cores, bounded samples) objects.  At N = 1 the line also carries, under
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`,
+`value`, `unit`, `ms_per_step`, ...); `--dump-outputs DIR` also writes what the last timed step returned (dump_outputs).
+Everything else needs `--full`: the `roofline` (dominant kernel: the 3x3-conv implicit GEMM), `f32_mfma_mode`, `chip`,
+`multi_gpu`, `precision` and `cpu_baseline` (oracle port on the host cores, bounded samples) objects, and, under
 "configs", at every N (`--no-also-configs` skips them), a short timing of the other BASELINE configurations -- #3
 MuLAN-velocity at GLOBAL batch 512 (strong scaling), #4 ImageNet-32 velocity_from_epsilon at 128 images per GPU (global
 1024 at N = 8), #5 the dense VLB evaluator (T = 1000) with the test images sharded over the ranks -- each training entry
@@ -24,6 +26,7 @@ with the convolution kernel's own roofline fraction, and of the SURVEY 8(f) wide
 "ode" (exact-likelihood evaluator: function evaluations/s, adaptive RK45 at rtol = atol = 1e-5, n_is = 1).
 """
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -60,14 +63,23 @@ def parse():
     ap.add_argument("--no-f32-mode", action="store_true", help="skip the reference measurement with exact-fp32 MFMA convs")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--also-configs", dest="also_configs", action="store_true", default=None,
-                    help="time BASELINE configs #3, #4, #5 after the headline (default: on at N = 1)")
+                    help="time BASELINE configs #3, #4, #5 after the headline (default: on with --full)")
     ap.add_argument("--no-also-configs", dest="also_configs", action="store_false")
     ap.add_argument("--also-steps", type=int, default=6, help="timed steps per extra training configuration")
     ap.add_argument("--configs-small", action="store_true",
                     help="test-sized extra configurations (global batch 32 / 8 per GPU, T = 64, tiny sampler / ODE batches): the "
                          "control flow of \"configs\" in seconds; the numbers it prints are not the configurations' numbers")
     ap.add_argument("--small-depth", type=int, default=0, help=argparse.SUPPRESS)   # tests only: ResBlocks per U-Net stage
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the convolution roofline steps, the exact-fp32 reference steps, "
+                         "chip telemetry, the multi-rank report, the precision probe, the CPU baseline and the extra "
+                         "configurations (default off: a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy: its metrics and "
+                         "a fixed, seeded sample of the parameter / EMA / gradient / Adam-moment buffers (float32 / float64)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     global TEST_DEPTH
     TEST_DEPTH = a.small_depth
     return a
@@ -465,9 +477,39 @@ def multi_rank_report(exp, state, batches, B, steps, warmup, world, dev, elapsed
     return rep
 
 
-def train_workload(a, rank, world, cfg_path, vdm_type, vfe, B, steps, warmup, f32_reference):
-    """W untimed + K timed train steps of one configuration (barrier + synchronize on both sides, MAX over ranks), then
-    the convolution kernel's roofline steps.  Returns a dict of raw results."""
+DUMP_SAMPLE = 1 << 20      # elements of each state buffer that --dump-outputs writes (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, state, metrics):
+    """--dump-outputs: what a caller of Experiment.train_step receives from the last timed step -- the metrics and the
+    new train state -- as DIR/<name>.npy.  The scalars are written whole (float64); of the flat parameter, EMA, gradient
+    and Adam-moment buffers (float32) the same DUMP_SAMPLE elements, drawn once from a fixed seed and kept in ascending
+    order (their indices: state_sample_index.npy), so that the files stay under 30 MB whatever the model's size."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = state.numel
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    idx_dev = torch.from_numpy(idx).to(state.flat.device)
+    arrays = {"state_sample_index": idx.astype(np.float64), "state_step": np.array([state.step], dtype=np.float64)}
+    for name, buf in (("params", state.flat), ("ema_params", state.ema), ("grad", state.grad), ("adam_mu", state.mu),
+                      ("adam_nu", state.nu)):
+        arrays["state_" + name] = buf.detach().index_select(0, idx_dev).float().cpu().numpy()
+    for k, v in metrics["scalars"].items():
+        arrays["metrics_" + k] = np.asarray(v.detach().double().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
+
+
+def train_workload(a, rank, world, cfg_path, vdm_type, vfe, B, steps, warmup, f32_reference, full=True, dump_dir=None):
+    """W untimed + K timed train steps of one configuration (barrier + synchronize on both sides, MAX over ranks); with
+    dump_dir, rank 0 then writes what the last timed step returned.  With full, the chip telemetry samples the timed
+    steps, and the multi-rank report, the convolution kernel's roofline steps and the exact-fp32 reference steps follow
+    them.  Returns a dict of raw results."""
     import torch
     import torch.distributed as dist
     from mulan_amd import ops
@@ -506,7 +548,7 @@ def train_workload(a, rank, world, cfg_path, vdm_type, vfe, B, steps, warmup, f3
         state, _ = exp.train_step(exp._train_rng, state, batches[i % len(batches)])
     torch.cuda.synchronize()
     barrier()
-    tele = Telemetry(torch.cuda.current_device())
+    tele = Telemetry(torch.cuda.current_device()) if full else contextlib.nullcontext()
     with tele:
         t0 = time.perf_counter()
         for i in range(steps):
@@ -515,16 +557,19 @@ def train_workload(a, rank, world, cfg_path, vdm_type, vfe, B, steps, warmup, f3
         barrier()
         elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
+    dumped = dump_outputs(dump_dir, state, m) if dump_dir and rank == 0 else None
     multi = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
-        multi = multi_rank_report(exp, state, batches, B, steps, warmup, world, dev, elapsed, elapsed_local, barrier)
+        if full:
+            multi = multi_rank_report(exp, state, batches, B, steps, warmup, world, dev, elapsed, elapsed_local, barrier)
     res = {"elapsed": elapsed, "multi": multi, "last_bpd": float(m["scalars"]["train_bpd"]), "prime": prime,
            "graph_used": bool(exp.hip_graph and exp._graphed is not None), "E": int(config.model.sm_n_embd),
            "n_layer": int(config.model.sm_n_layer), "conv_mode": ops.CONV_MODE, "f32_mode": None,
-           "graph_error": exp.graph_capture_error, "chip": tele.summary(), "elapsed_local": elapsed_local}
+           "graph_error": exp.graph_capture_error, "chip": tele.summary() if full else None,
+           "elapsed_local": elapsed_local, "dumped": dumped, "roof": None}
     red = exp.reducer
     if world > 1 and red.capture is not None:
         # how the replayed step hands its gradient buckets to the collectives (parallel.GradReducer): per bucket, how long
@@ -533,9 +578,10 @@ def train_workload(a, rank, world, cfg_path, vdm_type, vfe, B, steps, warmup, f3
                           "buckets": len(red.buckets), "marked": list(red.capture.get("order", [])),
                           "released_ms_before_graph_end": getattr(red, "bucket_leads", None),
                           "trial_replays_ms": getattr(red, "calibration", None)}
-    state, res["roof"] = conv_roofline(exp, state, batches[-1], a, rank, world, B, res["E"], elapsed / steps)
+    if full:
+        state, res["roof"] = conv_roofline(exp, state, batches[-1], a, rank, world, B, res["E"], elapsed / steps)
     # ---- the same step with the exact-fp32 MFMA convolution kernels (MULAN_CONV_MODE=f32), for reference
-    if f32_reference and world == 1 and ops.CONV_MODE != "f32":
+    if full and f32_reference and world == 1 and ops.CONV_MODE != "f32":
         saved = ops.CONV_MODE
         ops.CONV_MODE = "f32"
         exp.hip_graph = False               # (the captured graph holds the split-operand kernels)
@@ -820,17 +866,18 @@ def main():
     if strong and a.global_batch % world != 0:
         raise SystemExit(f"--global-batch {a.global_batch} is not divisible by {world} ranks")
     B = a.global_batch // world if strong else a.per_gpu_batch
-    head = train_workload(a, rank, world, a.config, a.vdm_type, a.vfe, B, a.steps, a.warmup, not a.no_f32_mode)
+    head = train_workload(a, rank, world, a.config, a.vdm_type, a.vfe, B, a.steps, a.warmup, not a.no_f32_mode,
+                          full=a.full, dump_dir=a.dump_outputs)
     elapsed, roof = head["elapsed"], head["roof"]
 
-    # ---- the other BASELINE configurations, driver-timed with the headline ("configs"), at every N:
+    # ---- the other BASELINE configurations, timed after the headline ("configs") with --full, at every N:
     #   "3": configs[2] as worded -- MuLAN-velocity CIFAR-10 at GLOBAL batch 512 (strong scaling: 512 / N images per GPU;
     #        at N = 1 also "3_at_64_per_gpu", the per-GPU size of the 8-GPU configuration, as in rounds 1-3);
     #   "4": configs[3] -- MuLAN-velocity ImageNet-32, velocity_from_epsilon, 128 images per GPU (global 128 N: the
     #        configuration's global batch of 1024 at N = 8);
     #   "5": configs[4] -- the dense evaluator itself, test images sharded over the ranks;
     #   "sampler", "ode": SURVEY 8(f) ranks 3 and 2 (rank 0's GPU only).
-    also = a.also_configs if a.also_configs is not None else True
+    also = a.also_configs if a.also_configs is not None else a.full
     extra = None
     out_of_sync = ["headline"] if (head["multi"] is not None and not head["multi"]["replicas_in_sync"]) else []
     if also:
@@ -890,9 +937,9 @@ def main():
         if out_of_sync:
             raise SystemExit(3)
         return
-    precision = split_precision_probe() if (ops.CONV_MODE == "f16x3" and not a.configs_small) else None
+    precision = split_precision_probe() if (a.full and ops.CONV_MODE == "f16x3" and not a.configs_small) else None
     cpu = None
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         # host leg in a child process (no GPU touched there) with a hard wall-clock bound
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--config", a.config, "--vdm-type",
@@ -951,7 +998,7 @@ def main():
         "oracle_pin": "unpinned: the reference has no golden vectors, JAX / Flax are not installable here and no "
                       "released checkpoint is in the image (tools/verify_checkpoint.py pins it in one command)",
         "roofline": roof, "f32_mfma_mode": head["f32_mode"], "precision": precision, "chip": head["chip"],
-        "multi_gpu": head["multi"], "cpu_baseline": cpu, "configs": extra,
+        "multi_gpu": head["multi"], "cpu_baseline": cpu, "configs": extra, "full": a.full,
     }
     if out_of_sync:
         out["replicas_out_of_sync"] = out_of_sync

@@ -625,34 +625,69 @@ def test_no_mfma_data_hazard_in_the_built_objects(built_lib):
     assert found == [], found[:5]
 
 
-def test_bench_self_launches_for_several_gpus(monkeypatch):
+_SELF_LAUNCH_PROBE = r"""
+import importlib.util, json, os, subprocess, sys
+spec = importlib.util.spec_from_file_location("bench_under_test", sys.argv[1])
+bench = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(bench)
+seen = {}
+def fake_run(cmd, env=None, **kw):
+    seen["cmd"], seen["env"] = cmd, env
+    return subprocess.CompletedProcess(cmd, 7)
+subprocess.run = fake_run
+sys.argv = ["bench.py", "--gpus", "8", "--steps", "3", "--warmup", "1"]
+os.environ.pop("WORLD_SIZE", None)
+code = "returned"
+try:
+    bench.main()
+except SystemExit as e:
+    code = e.code
+print(json.dumps({"code": code, "cmd": seen["cmd"], "env": seen["env"],
+                  "cuda_initialized": "torch.cuda" in sys.modules and __import__("torch").cuda.is_initialized()}))
+"""
+
+
+def test_bench_self_launches_for_several_gpus():
     """`python bench.py --gpus 8` without WORLD_SIZE in the environment starts `python -m torch.distributed.run
     --nproc-per-node 8 ... bench.py <same arguments>` as a CHILD process (the parent never initialises the GPU) and
-    exits with the child's code; with WORLD_SIZE set (it is one of the ranks) it does not."""
-    import importlib.util
+    exits with the child's code; with WORLD_SIZE set (it is one of the ranks) it does not.  The parent runs in a fresh
+    interpreter (subprocess.run replaced by a recorder there): in this one another test may have initialised the GPU."""
+    import json
     import subprocess
     import sys
-    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    seen = {}
-
-    def fake_run(cmd, env=None, **kw):
-        seen["cmd"], seen["env"] = cmd, env
-        return subprocess.CompletedProcess(cmd, 7)
-    monkeypatch.setattr(subprocess, "run", fake_run)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "3", "--warmup", "1"])
-    monkeypatch.delenv("WORLD_SIZE", raising=False)
-    with pytest.raises(SystemExit) as e:
-        bench.main()
-    assert e.value.code == 7
+    r = subprocess.run([sys.executable, "-c", _SELF_LAUNCH_PROBE, os.path.join(ROOT, "bench.py")], capture_output=True,
+                       text=True, timeout=300, cwd=ROOT)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    seen = json.loads(lines[0])
+    assert seen["code"] == 7
     cmd = seen["cmd"]
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nnodes=1" in cmd and cmd[cmd.index("--nproc-per-node") + 1] == "8"
     # the rendezvous port is torchrun's own choice (--standalone: no bind / close / reuse gap), on the loop-back address
     assert "--standalone" in cmd and cmd[cmd.index("--local-addr") + 1] == "127.0.0.1" and "--master-port" not in cmd
     assert cmd[-7:] == [os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
-    assert "torch.cuda" not in sys.modules or not __import__("torch").cuda.is_initialized()
+    assert seen["cuda_initialized"] is False
+
+
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """a plain `python bench.py --steps K --warmup W` measures the headline only: --full (the roofline / reference /
+    telemetry / CPU-baseline / extra-configuration legs) and --dump-outputs are off unless asked for, and --steps is
+    the number of timed steps (at least one)"""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2 and a.also_configs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
 
 
 def test_load_flax_reads_bytes_it_did_not_write():

@@ -461,11 +461,11 @@ def test_bench_ranks_share_one_gpu(graph, launcher, configs, world):
     it (the host could not keep up with an eager step); "0": MULAN_HIP_GRAPH=0, the eager step whose all-reduce overlaps
     the backward pass (the default from 96 images per rank at E = 128).  launcher = "self": plain `python bench.py --gpus 2` -- the bench starts
     torch.distributed.run itself as a child process and relays rank 0's line (the reference needs no launcher either,
-    ldm/experiment.py:89-95); "torchrun": the driver's command line.  configs: the default at every N -- the line also
+    ldm/experiment.py:89-95); "torchrun": the driver's command line.  configs: --full's default at every N -- the line also
     carries BASELINE configs[2] at a GLOBAL batch (strong scaling), configs[3] per rank, configs[4] through the sharded
     evaluator (eval_bpd_dense_sampling, one (sum, count) all-reduce) and the sampler / ODE entries -- here at the test
-    sizes of --configs-small (the full sizes run in every `python bench.py`: profiles/r04_bench_n1.json.log); False:
-    --no-also-configs."""
+    sizes of --configs-small (the full sizes run in every `python bench.py --full`: profiles/r04_bench_n1.json.log); False:
+    --no-also-configs.  All three pass --full: the roofline, chip and multi-rank records are --full's."""
     import json
     import os
     import socket
@@ -487,8 +487,11 @@ def test_bench_ranks_share_one_gpu(graph, launcher, configs, world):
     # all three use --small-depth (1 or 2 ResnetBlocks per stage: the control flow, not the sizes -- the full depth runs in
     # every other whole-model test and in every `python bench.py`); 8 ranks: 4 images per rank
     per = 8 if world == 2 else 4
-    args = [os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--per-gpu-batch", str(per),
-            "--also-steps", "2"] + (["--configs-small", "--small-depth", "1"] if configs
+    # the eager step over gloo: its steps without collectives (multi_gpu, as many as timed ones, up to 10) are ~8x shorter
+    # than the timed ones, so with two of each a single host stall of ~1 s decided the scaling-efficiency bound; ten each
+    steps, warmup = ("10", "3") if graph == "0" else ("2", "1")
+    args = [os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", steps, "--warmup", warmup, "--per-gpu-batch", str(per),
+            "--also-steps", "2", "--full"] + (["--configs-small", "--small-depth", "1"] if configs
                                     else ["--no-also-configs", "--small-depth", "2"])
     if launcher == "self":
         cmd = [sys.executable] + args
@@ -532,6 +535,45 @@ def test_bench_ranks_share_one_gpu(graph, launcher, configs, world):
         assert max(ov["released_ms_before_graph_end"]) > 0.5          # some bucket was released before the graph ended
     else:      # eager overlapped step, or the default multi-rank replay: collectives behind the graph
         assert ov is None
+
+
+@pytest.mark.timeout(600)
+def test_plain_bench_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: the headline line with every --full record left null, and
+    --dump-outputs writes what the last timed step returned -- float32 / float64 arrays, under 64 MB, finite, its
+    train_bpd the line's last_train_bpd, its optimizer step count the set-up + W + K steps that ran."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("MULAN_HIP_GRAPH", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MULAN_GRAPH_OVERLAP"):
+        env.pop(k, None)
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--per-gpu-batch", "8", "--small-depth", "1", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd=root)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["metric"] == "train images/sec" and out["unit"] == "images/s" and out["higher_is_better"] is True
+    assert abs(out["value"] - 8 / (out["ms_per_step"] * 1e-3)) < 0.02 * out["value"]
+    for k in ("roofline", "f32_mfma_mode", "precision", "chip", "multi_gpu", "cpu_baseline", "configs"):
+        assert out[k] is None, k
+    files = sorted(os.listdir(out_dir))
+    assert {"state_params.npy", "state_ema_params.npy", "state_grad.npy", "state_adam_mu.npy", "state_adam_nu.npy",
+            "state_sample_index.npy", "state_step.npy", "metrics_train_bpd.npy"} <= set(files), files
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 * 2 ** 20
+    arrays = {f[:-4]: np.load(out_dir / f) for f in files}
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64) and np.isfinite(arr).all(), name
+    n = arrays["state_params"].size
+    assert n > 0 and all(arrays[k].shape == (n,) for k in ("state_ema_params", "state_grad", "state_adam_mu", "state_adam_nu"))
+    assert float(np.abs(arrays["state_grad"]).max()) > 0 and float(arrays["state_adam_nu"].max()) > 0
+    assert abs(float(arrays["metrics_train_bpd"]) - out["last_train_bpd"]) < 1e-4
+    assert int(arrays["state_step"][0]) == out["setup_steps"] + 1 + 3
 
 
 @pytest.mark.timeout(900)

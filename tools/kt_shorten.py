@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """dev: the tail of a rocprofv3 --kernel-trace CSV as the short table tools/step_timeline.py reads (name, queue, start, end):
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -o kt -- python3 bench.py --steps 6 --warmup 3 ...
-    python tools/kt_shorten.py gpurun_out/kt/kt_kernel_trace.csv gpurun_out/kt_tail.csv [rows = 6000]"""
+    rocprofv3 --kernel-trace --output-format csv -d out/kt -o kt -- python3 bench.py --full --steps 6 --warmup 3 ...
+    python tools/kt_shorten.py out/kt/kt_kernel_trace.csv out/kt_tail.csv [rows = 6000]"""
 import csv
 import sys
 

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """dev: one replayed train step out of a shortened kernel trace (name, queue, start, end in ns; written by the recipe in
 profiles/README.md): time per queue, time with >= 1 / >= 2 kernels running, gaps, and the head / tail of the two
-backward streams.   python tools/step_timeline.py gpurun_out/kt_tail.csv [--back N] [--list ms0 ms1]
-(bench.py ends with two eager steps of conv_roofline -- as run with event timers, then serial: --back 3 is a replayed step)"""
+backward streams.   python tools/step_timeline.py out/kt_tail.csv [--back N] [--list ms0 ms1]
+(bench.py --full ends with two eager steps of conv_roofline -- as run with event timers, then serial: --back 3 is a replayed step)"""
 import collections
 import csv
 import sys
