@@ -539,6 +539,23 @@ int mulan_topk_fwd(const float* logits, const float* gnoise, float* emb, float* 
                    int B, int L, int k, float tau, mulan_stream_t stream);
 int mulan_topk_bwd(const float* logits, const float* soft, const float* nrm, const float* demb, const float* dkl,
                    float* dlogits, int B, int L, mulan_stream_t stream);
+/* _gumbel_embedding_and_loss (model_mulan_velocity.py:68-92, model_mulan_epsilon.py:195-219), latent_type 'gumbel':
+ * y = (logits + gnoise) / tau, soft = softmax(y), hard = one_hot(argmax y) (first index on ties),
+ * emb = (hard - soft) + soft, kl = sum q (log q - log(1/L)) with q = softmax(logits).  gnoise: [B,L] Gumbel draws;
+ * tau: ONE fp32 on the device (read when the kernel runs); soft [B,L] is kept for the backward pass.  L <= 64. */
+int mulan_gumbel_latent_fwd(const float* logits, const float* gnoise, const float* tau, float* emb, float* kl,
+                            float* soft, int B, int L, mulan_stream_t stream);
+/* dlogits = softmax Jacobian of demb (straight-through) / tau + dkl q (log q + log L - kl) */
+int mulan_gumbel_latent_bwd(const float* logits, const float* soft, const float* tau, const float* demb,
+                            const float* dkl, float* dlogits, int B, int L, mulan_stream_t stream);
+/* latent_type 'gaussian' (_get_embedding_and_kl_z, model_mulan_velocity.py:125-139, model_mulan_epsilon.py:257-271;
+ * the softplus head of UnetEncoderGaussian, model_mulan_epsilon.py:24-80): var = softplus(s), emb = mu + sqrt(var) eps_z,
+ * kl = 0.5 sum (mu^2 + var - log var - 1).  mu, s, eps_z, emb: [B,L]; kl: [B].  L <= 64. */
+int mulan_gaussian_latent_fwd(const float* mu, const float* s, const float* eps_z, float* emb, float* kl, int B, int L,
+                              mulan_stream_t stream);
+/* dmu = demb + dkl mu; ds = (demb eps_z / (2 sqrt var) + 0.5 dkl (1 - 1/var)) sigmoid(s) */
+int mulan_gaussian_latent_bwd(const float* mu, const float* s, const float* eps_z, const float* demb, const float* dkl,
+                              float* dmu, float* ds, int B, int L, mulan_stream_t stream);
 
 /* ---- optimiser + RNG ------------------------------------------------------------------------- */
 /* TrainState.apply_gradients (ldm/train_state.py:70-102) with optax.adamw of ldm/experiment.py:132-182

@@ -6,6 +6,8 @@
 //   diffloss   : velocity / velocity-from-epsilon / epsilon diffusion loss
 //                (model_mulan_velocity.py:246-260; model_mulan_epsilon.py:338-355; model_vdm.py:156-170)
 //   topk       : relaxed top-k straight-through latent + KL to uniform (model_mulan_velocity.py:78-120)
+//   gumbel     : straight-through Gumbel-softmax one-hot latent + KL to uniform (model_mulan_velocity.py:68-92)
+//   gaussian   : reparameterised Gaussian latent + KL to N(0, I) (model_mulan_velocity.py:132-138)
 // Every backward is analytic; noise is an explicit input so the CPU oracle sees identical draws.
 #include "common.h"
 
@@ -356,6 +358,100 @@ __global__ __launch_bounds__(64) void topk_bwd_kernel(TkArgs p) {
   if (on) p.dlogits[(size_t)b * L + j] = dl + p.dkl[b] * q * (term - klv);
 }
 
+// ------------------------------------------------------------------ Gumbel-softmax latent
+// One 64-lane block per row; L <= 64 logits.  tau is read from device memory (a stream-ordered parameter: the replayed
+// train step anneals it without a new capture).
+struct GbArgs {
+  const float* logits; const float* gnoise; const float* tau; int L;
+  float* emb; float* kl; float* soft;               // [B,L],[B],[B,L]
+  // bwd
+  const float* demb; const float* dkl; float* dlogits;
+};
+
+// KL(softmax(logits) || uniform) of _gumbel_kl_loss, in the order topk_fwd_kernel computes it; q and log q - log(1/L)
+// are returned for the backward pass
+__device__ __forceinline__ float kl_uniform(float lg, bool on, int L, float& q, float& term) {
+  const float mx = wave_max(on ? lg : -INFINITY);
+  const float ex = on ? expf(lg - mx) : 0.f;
+  const float se = wave_sum(ex);
+  const float logq = (lg - mx) - logf(se);
+  q = ex / se;
+  term = logq - logf(1.0f / (float)L);
+  return wave_sum(on ? q * term : 0.f);
+}
+
+__global__ __launch_bounds__(64) void gumbel_latent_fwd_kernel(GbArgs p) {
+  const int b = blockIdx.x, j = threadIdx.x, L = p.L;
+  const bool on = j < L;
+  const size_t o = (size_t)b * L + j;
+  const float lg = on ? p.logits[o] : 0.f;
+  float q, term;
+  const float klv = kl_uniform(lg, on, L, q, term);
+  // _get_gumbel_embedding (model_mulan_velocity.py:68-76): y = (logits + g) / tau
+  const float y = on ? (lg + p.gnoise[o]) / *p.tau : -INFINITY;
+  const float my = wave_max(y);
+  const float ey = on ? expf(y - my) : 0.f;
+  const float soft = ey / wave_sum(ey);
+  // jnp.argmax: the first index of the maximum
+  const unsigned long long at_max = __ballot(on && y == my);
+  const int first = at_max ? __ffsll((long long)at_max) - 1 : 0;
+  if (on) {
+    const float hard = j == first ? 1.f : 0.f;
+    p.emb[o] = (hard - soft) + soft;
+    p.soft[o] = soft;
+  }
+  if (j == 0) p.kl[b] = klv;
+}
+
+__global__ __launch_bounds__(64) void gumbel_latent_bwd_kernel(GbArgs p) {
+  const int b = blockIdx.x, j = threadIdx.x, L = p.L;
+  const bool on = j < L;
+  const size_t o = (size_t)b * L + j;
+  const float lg = on ? p.logits[o] : 0.f;
+  const float soft = on ? p.soft[o] : 0.f;
+  const float ds = on ? p.demb[o] : 0.f;      // straight-through: d emb / d soft = 1
+  const float dot = wave_sum(soft * ds);
+  const float dl = soft * (ds - dot) / *p.tau;
+  float q, term;
+  const float klv = kl_uniform(lg, on, L, q, term);
+  if (on) p.dlogits[o] = dl + p.dkl[b] * q * (term - klv);
+}
+
+// ------------------------------------------------------------------ Gaussian latent
+// UnetEncoderGaussian's softplus head (model_mulan_epsilon.py:74-80) and the reparameterised draw + KL to N(0, I) of
+// _get_embedding_and_kl_z (model_mulan_velocity.py:132-138).  s: the pre-softplus head; var = softplus(s).
+struct GsArgs {
+  const float* mu; const float* s; const float* eps; int L;
+  float* emb; float* kl;                            // [B,L],[B]
+  // bwd
+  const float* demb; const float* dkl; float* dmu; float* ds;
+};
+
+__global__ __launch_bounds__(64) void gaussian_latent_fwd_kernel(GsArgs p) {
+  const int b = blockIdx.x, j = threadIdx.x, L = p.L;
+  const bool on = j < L;
+  const size_t o = (size_t)b * L + j;
+  float t = 0.f;
+  if (on) {
+    const float mu = p.mu[o], var = softplus_f(p.s[o]);
+    p.emb[o] = mu + sqrtf(var) * p.eps[o];
+    t = mu * mu + var - logf(var) - 1.f;
+  }
+  const float klv = 0.5f * wave_sum(t);
+  if (j == 0) p.kl[b] = klv;
+}
+
+__global__ __launch_bounds__(64) void gaussian_latent_bwd_kernel(GsArgs p) {
+  const int b = blockIdx.x, j = threadIdx.x, L = p.L;
+  if (j >= L) return;
+  const size_t o = (size_t)b * L + j;
+  const float mu = p.mu[o], s = p.s[o], var = softplus_f(s);
+  const float de = p.demb[o], dk = p.dkl[b];
+  p.dmu[o] = de + dk * mu;
+  const float dvar = de * p.eps[o] / (2.f * sqrtf(var)) + 0.5f * dk * (1.f - 1.f / var);
+  p.ds[o] = dvar * sigmoid_f(s);
+}
+
 inline int nblocks(size_t n) { size_t b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b ? b : 1)); }
 
 }  // namespace
@@ -437,5 +533,33 @@ MULAN_API int mulan_topk_bwd(const float* logits, const float* soft, const float
   TkArgs a{logits, nullptr, B, L, 0, 0.f, nullptr, nullptr, const_cast<float*>(soft), const_cast<float*>(nrm), demb, dkl,
            dlogits};
   hipLaunchKernelGGL(topk_bwd_kernel, dim3(B), dim3(64), 0, stream, a);
+  MULAN_CHECK_LAUNCH();
+}
+MULAN_API int mulan_gumbel_latent_fwd(const float* logits, const float* gnoise, const float* tau, float* emb, float* kl,
+                                      float* soft, int B, int L, hipStream_t stream) {
+  if (L > 64 || L <= 0 || B <= 0 || !tau) return (int)hipErrorInvalidValue;
+  GbArgs a{logits, gnoise, tau, L, emb, kl, soft, nullptr, nullptr, nullptr};
+  hipLaunchKernelGGL(gumbel_latent_fwd_kernel, dim3(B), dim3(64), 0, stream, a);
+  MULAN_CHECK_LAUNCH();
+}
+MULAN_API int mulan_gumbel_latent_bwd(const float* logits, const float* soft, const float* tau, const float* demb,
+                                      const float* dkl, float* dlogits, int B, int L, hipStream_t stream) {
+  if (L > 64 || L <= 0 || B <= 0 || !tau) return (int)hipErrorInvalidValue;
+  GbArgs a{logits, nullptr, tau, L, nullptr, nullptr, const_cast<float*>(soft), demb, dkl, dlogits};
+  hipLaunchKernelGGL(gumbel_latent_bwd_kernel, dim3(B), dim3(64), 0, stream, a);
+  MULAN_CHECK_LAUNCH();
+}
+MULAN_API int mulan_gaussian_latent_fwd(const float* mu, const float* s, const float* eps_z, float* emb, float* kl, int B,
+                                        int L, hipStream_t stream) {
+  if (L > 64 || L <= 0 || B <= 0) return (int)hipErrorInvalidValue;
+  GsArgs a{mu, s, eps_z, L, emb, kl, nullptr, nullptr, nullptr, nullptr};
+  hipLaunchKernelGGL(gaussian_latent_fwd_kernel, dim3(B), dim3(64), 0, stream, a);
+  MULAN_CHECK_LAUNCH();
+}
+MULAN_API int mulan_gaussian_latent_bwd(const float* mu, const float* s, const float* eps_z, const float* demb,
+                                        const float* dkl, float* dmu, float* ds, int B, int L, hipStream_t stream) {
+  if (L > 64 || L <= 0 || B <= 0) return (int)hipErrorInvalidValue;
+  GsArgs a{mu, s, eps_z, L, nullptr, nullptr, demb, dkl, dmu, ds};
+  hipLaunchKernelGGL(gaussian_latent_bwd_kernel, dim3(B), dim3(64), 0, stream, a);
   MULAN_CHECK_LAUNCH();
 }

@@ -64,7 +64,8 @@ class GraphedStep:
     is replayed with a single launch.  Everything that changes from step to step reaches the kernels through device
     memory written before the replay ("stream-ordered parameters"):
       * the uint8 batch and the noise tensors (eps_0, eps, Gamma draws) live in static buffers filled eagerly;
-      * t0 of the antithetic time grid is a 0-dim device tensor;
+      * t0 of the antithetic time grid is a 0-dim device tensor, and so is the Gumbel-softmax temperature tau of
+        latent_type 'gumbel' (annealed with the step count, which the capture does not see);
       * the two dropout seeds are int64 device slots read by the GroupNorm kernels (mulan_groupnorm_*_dyn);
       * learning rate and Adam bias corrections are a float device array read by mulan_adamw_ema_step_dyn.
     The keys are derived on the host exactly as the eager step derives them (Experiment_VDM.step_keys), so a replayed
@@ -82,21 +83,27 @@ class GraphedStep:
         cfg = exp.model.config
         self.inputs = {k: torch.empty_like(v) for k, v in batch.items()}
         self.need_gamma = getattr(cfg, 'reparam_type', 'true') == 'true' and hasattr(cfg, 'latent_k')
-        self.gumbel = getattr(cfg, 'topk_noise_type', 'gamma') == 'gumbel'
+        self.latent_type = getattr(cfg, 'latent_type', 'topk')
+        self.gumbel = self.latent_type == 'gumbel' or (self.latent_type == 'topk' and
+                                                        getattr(cfg, 'topk_noise_type', 'gamma') == 'gumbel')
         self.noise = {'t0': torch.zeros((), device=dev, dtype=torch.float32),
                       'eps_0': torch.empty((B, 3072), device=dev, dtype=torch.float32),
                       'eps': torch.empty((B, 3072), device=dev, dtype=torch.float32)}
         if not cfg.antithetic_time_sampling:
             self.noise['t'] = torch.empty((B,), device=dev, dtype=torch.float32)
         if self.need_gamma:
-            if self.gumbel:
+            if self.latent_type == 'gaussian':
+                self.noise['eps_z'] = torch.empty((B, cfg.latent_size), device=dev, dtype=torch.float32)
+            elif self.gumbel:
                 self.noise['gumbel'] = torch.empty((B, cfg.latent_size), device=dev, dtype=torch.float32)
             else:
                 self.noise['gamma_raw'] = torch.empty((10, B, cfg.latent_size), device=dev, dtype=torch.float32)
+            if self.latent_type == 'gumbel':
+                self.noise['tau'] = torch.ones((), device=dev, dtype=torch.float32)
         self.seeds = torch.zeros(2, device=dev, dtype=torch.int64)
         self.dyn = torch.zeros(4, device=dev, dtype=torch.float32)
         self.h_seeds = torch.zeros(2, dtype=torch.int64).pin_memory()
-        self.h_dyn = torch.zeros(5, dtype=torch.float32).pin_memory()       # lr, bc1, bc2, 0, t0
+        self.h_dyn = torch.zeros(6, dtype=torch.float32).pin_memory()       # lr, bc1, bc2, 0, t0, tau
         # collectives inside the graph (see GRAPH_COLLECTIVES): RCCL process groups only
         self.captured_collectives = bool(exp.world > 1 and exp.graph_collectives and exp.reducer.enabled and
                                          exp.reducer.sync_ops)
@@ -184,6 +191,8 @@ class GraphedStep:
             self.noise['gamma_raw'].copy_(keys['gamma'].gamma(1.0 / cfg.latent_k, (10, B, cfg.latent_size), dev))
         if 'gumbel' in self.noise:
             self.noise['gumbel'].copy_(ops.noise(tuple(self.noise['gumbel'].shape), keys['gamma'].v, 0, dev, "gumbel"))
+        if 'eps_z' in self.noise:
+            self.noise['eps_z'].copy_(keys['gamma'].normal(tuple(self.noise['eps_z'].shape), dev))
         ops.randn(None, keys['eps_0'].v, 0, dev, out=self.noise['eps_0'])
         ops.randn(None, keys['eps'].v, 0, dev, out=self.noise['eps'])
         to_i64 = lambda v: v - (1 << 64) if v >= (1 << 63) else v
@@ -196,6 +205,10 @@ class GraphedStep:
         self.seeds.copy_(self.h_seeds, non_blocking=True)
         self.dyn.copy_(self.h_dyn[:4], non_blocking=True)
         self.noise['t0'].copy_(self.h_dyn[4], non_blocking=True)
+        if 'tau' in self.noise:
+            from .model import gumbel_tau
+            self.h_dyn[5] = gumbel_tau(state.step)
+            self.noise['tau'].copy_(self.h_dyn[5], non_blocking=True)
         self.copied.record()
 
     def step(self, base_rng, state, batch):

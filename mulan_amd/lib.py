@@ -106,6 +106,10 @@ SIGNATURES = {
     "mulan_diffloss_bwd": [I, P, P, P, I, P, P, P, P, P, P, P, P, I, I, P],
     "mulan_topk_fwd": [P, P, P, P, P, P, I, I, I, F, P],
     "mulan_topk_bwd": [P, P, P, P, P, P, I, I, P],
+    "mulan_gumbel_latent_fwd": [P, P, P, P, P, P, I, I, P],
+    "mulan_gumbel_latent_bwd": [P, P, P, P, P, P, I, I, P],
+    "mulan_gaussian_latent_fwd": [P, P, P, P, P, I, I, P],
+    "mulan_gaussian_latent_bwd": [P, P, P, P, P, P, P, I, I, P],
     "mulan_ancestral_step": [P, P, P, P, P, P, Z, I, I, P],
     "mulan_decode_argmax": [P, P, P, Z, I, P],
     "mulan_decode_sample": [P, P, P, Z, I, U, U, P],

@@ -368,7 +368,8 @@ def score_unet(p, cfg, z, g_t, conditioning, drop, time=False):
 
 
 def unet_encoder(p, cfg, f, drop):
-    """UnetEncoder.__call__ (ldm/model_mulan_epsilon.py:101-154): f [B,1024,3] -> logits [B,latent_size]"""
+    """UnetEncoder.__call__ (ldm/model_mulan_epsilon.py:101-154): f [B,1024,3] -> logits [B,latent_size]; latent_type
+    'gaussian': UnetEncoderGaussian (ldm/model_mulan_epsilon.py:24-80) -> (mu, s) with s the pre-softplus head"""
     B = f.shape[0]
     E = cfg.sm_n_embd
     t = torch.zeros(B, device=f.device)
@@ -377,7 +378,19 @@ def unet_encoder(p, cfg, f, drop):
     h = ops.group_norm(h, None, p["GroupNorm_0"]["scale"], p["GroupNorm_0"]["bias"], act=True)
     h = ops.conv3x3(h, p["conv_out"]["kernel"], p["conv_out"]["bias"])          # [B,1024,1]
     h = ops.silu(h.view(B, HW))
+    if cfg.latent_type == 'gaussian':
+        return (ops.linear(h, p["dense_layer_final_mu"]["kernel"], p["dense_layer_final_mu"]["bias"]),
+                ops.linear(h, p["dense_layer_final_sigma"]["kernel"], p["dense_layer_final_sigma"]["bias"]))
     return ops.linear(h, p["dense_layer_final"]["kernel"], p["dense_layer_final"]["bias"])
+
+
+LATENT_TYPES = ('topk', 'gumbel', 'gaussian')
+
+
+def gumbel_tau(step):
+    """the Gumbel-softmax temperature max(0.5, exp(-1e-5 step)) in fp32, as jnp evaluates it
+    (ldm/model_mulan_velocity.py:87-90)"""
+    return float(np.maximum(np.float32(0.5), np.exp(np.float32(-1e-5) * np.float32(step))))
 
 
 def poly_coefficients(p, emb):
@@ -402,10 +415,12 @@ class _VDMBase:
 
     def _noise(self, rngs, noise, B, device, need_gamma):
         """Draw (t0, raw Gamma, eps_0, eps) in the reference's make_rng('sample') order
-        (ldm/model_mulan_velocity.py:195, :95-96 via :210, :223, :235) unless given explicitly."""
+        (ldm/model_mulan_velocity.py:195, :95-96 via :210, :223, :235) unless given explicitly.  The latent's draw takes
+        the second slot whatever the latent: Gumbel noise [B,L] for latent_type 'gumbel' (:70), eps_z [B,L] for
+        'gaussian' (:134)."""
         noise = dict(noise or {})
         key = rngs.get("sample") if rngs else None
-        gkey = "gumbel" if self.config.topk_noise_type == 'gumbel' else "gamma_raw"
+        gkey = self._latent_noise_key()
         tkey = "t0" if self.config.antithetic_time_sampling else "t"
         if any(k not in noise for k in (tkey, "eps_0", "eps")) or (need_gamma and gkey not in noise):
             if key is None:
@@ -416,13 +431,23 @@ class _VDMBase:
                 noise.setdefault("t", ops.noise((B,), k_t.v, 0, device, "uniform"))
             if need_gamma:
                 cfg = self.config
-                if cfg.topk_noise_type == 'gumbel':
+                if gkey == "eps_z":
+                    noise.setdefault("eps_z", k_g.normal((B, cfg.latent_size), device))
+                elif gkey == "gumbel":
                     noise.setdefault("gumbel", ops.noise((B, cfg.latent_size), k_g.v, 0, device, "gumbel"))
                 else:
                     noise.setdefault("gamma_raw", k_g.gamma(1.0 / cfg.latent_k, (10, B, cfg.latent_size), device))
             noise.setdefault("eps_0", k_0.normal((B, D), device))
             noise.setdefault("eps", k_e.normal((B, D), device))
         return noise
+
+    def _latent_noise_key(self):
+        cfg = self.config
+        if getattr(cfg, 'latent_type', 'topk') == 'gaussian':
+            return "eps_z"
+        if getattr(cfg, 'latent_type', 'topk') == 'gumbel' or cfg.topk_noise_type == 'gumbel':
+            return "gumbel"
+        return "gamma_raw"
 
     def _times(self, noise, B, device):
         cfg = self.config
@@ -453,11 +478,12 @@ class MulanVDM(_VDMBase):
         assert parameterization in ("velocity", "epsilon")
         self.parameterization = parameterization
         c = config
-        if c.latent_type != 'topk' or c.encoder != 'unet' or c.gamma_type != 'poly_fixedend':
+        if c.latent_type not in LATENT_TYPES or c.encoder != 'unet' or c.gamma_type != 'poly_fixedend':
             raise NotImplementedError(
-                "hot path covers latent_type=topk, encoder=unet, gamma_type=poly_fixedend (the shipped configs); "
+                "hot path covers latent_type=topk|gumbel|gaussian, encoder=unet, gamma_type=poly_fixedend; "
                 f"got {c.latent_type}/{c.encoder}/{c.gamma_type}")
-        if c.topk_noise_type not in ('gamma', 'gumbel') or (c.topk_noise_type == 'gumbel' and parameterization != "epsilon"):
+        if c.latent_type == 'topk' and (c.topk_noise_type not in ('gamma', 'gumbel') or
+                                        (c.topk_noise_type == 'gumbel' and parameterization != "epsilon")):
             raise ValueError("topk_noise_type: 'gamma' (both models) or 'gumbel' (model_mulan_epsilon only, "
                              "ldm/model_mulan_epsilon.py:236-239)")
         if parameterization == "velocity" and c.sm_n_timesteps != 0:
@@ -471,7 +497,11 @@ class MulanVDM(_VDMBase):
         temb = 3 * E if c.unet_type == 'ldm' else E
         score = _unet_init(gen, E, c.sm_n_layer, temb + K, 3, True, c.with_attention)
         enc = _unet_init(gen, E, c.forward_n_layer, E + 1, 1, False, c.with_attention)
-        enc["dense_layer_final"] = _dense(gen, HW, c.latent_size)
+        if c.latent_type == 'gaussian':      # UnetEncoderGaussian (ldm/model_mulan_epsilon.py:76-79)
+            enc["dense_layer_final_mu"] = _dense(gen, HW, c.latent_size)
+            enc["dense_layer_final_sigma"] = _dense(gen, HW, c.latent_size)
+        else:
+            enc["dense_layer_final"] = _dense(gen, HW, c.latent_size)
         lat = c.latent_size if c.reparam_type == 'true' else 10
         gamma = {"dense_1": _dense(gen, lat, D), "dense_2": _dense(gen, D, D),
                  "dense_out_a": _dense(gen, D, D, zero=True), "dense_out_b": _dense(gen, D, D),
@@ -502,10 +532,20 @@ class MulanVDM(_VDMBase):
         if cfg.reparam_type == 'true':
             if same_image and deterministic and B > 1:
                 logits = unet_encoder(params["encoder_model"], cfg, f[:1].contiguous(), _Drop(None, 0.0))
-                logits = logits.expand(B, logits.shape[1]).contiguous()
+                if cfg.latent_type == 'gaussian':        # both heads; eps_z still differs per row
+                    logits = tuple(h.expand(B, h.shape[1]).contiguous() for h in logits)
+                else:
+                    logits = logits.expand(B, logits.shape[1]).contiguous()
             else:
                 logits = unet_encoder(params["encoder_model"], cfg, f, _Drop(k_enc, cfg.sm_pdrop))
-            if cfg.topk_noise_type == 'gumbel':
+            if cfg.latent_type == 'gaussian':           # ldm/model_mulan_velocity.py:132-138
+                emb, kl_z = ops.gaussian_embedding(logits[0], logits[1], noise["eps_z"])
+            elif cfg.latent_type == 'gumbel':           # ldm/model_mulan_velocity.py:85-92
+                tau = noise.get("tau")
+                if tau is None:
+                    tau = torch.full((), gumbel_tau(step), device=dev, dtype=torch.float32)
+                emb, kl_z = ops.gumbel_embedding(logits, noise["gumbel"], tau)
+            elif cfg.topk_noise_type == 'gumbel':
                 emb, kl_z = ops.topk_embedding(logits, noise["gumbel"], cfg.latent_k, tau=-1.0)
             else:
                 emb, kl_z = ops.topk_embedding(logits, noise["gamma_raw"], cfg.latent_k)
@@ -541,10 +581,14 @@ class MulanVDM(_VDMBase):
 
     # ---- ancestral sampler (ldm/model_mulan_velocity.py:270-368, ldm/model_mulan_epsilon.py:365-460) ----------
     def deterministic_embedding(self, B, device):
-        """_get_deterministic_embedding for latent_type = topk: the first latent_k entries set"""
+        """_get_deterministic_embedding (ldm/model_mulan_velocity.py:270-279): topk: the first latent_k entries set;
+        gumbel: one_hot(ones(B)), i.e. entry 1 set; gaussian: zeros"""
         c = self.config
         emb = torch.zeros((B, c.latent_size), device=device, dtype=torch.float32)
-        emb[:, :c.latent_k] = 1.0
+        if c.latent_type == 'gumbel':
+            emb[:, 1] = 1.0
+        elif c.latent_type == 'topk':
+            emb[:, :c.latent_k] = 1.0
         return emb
 
     def sample_coefficients(self, params, embedding):
@@ -626,7 +670,8 @@ class MulanVDM(_VDMBase):
 
     # ---- probability-flow ODE (ldm/model_mulan_velocity.py:51-53, 393-421; ldm/model_mulan_epsilon.py:459-478) ----
     def apply_encoder(self, params, images_u8):
-        """VDM.apply_encoder: encoder logits [B, latent_size] of integer images"""
+        """VDM.apply_encoder: encoder logits [B, latent_size] of integer images (latent_type 'gaussian': the heads
+        (mu, s), s before the softplus)"""
         x = images_u8.reshape(-1, D).contiguous()
         with torch.no_grad():
             return unet_encoder(params["encoder_model"], self.config, encode_images(x), _Drop(None, 0.0))
@@ -636,6 +681,10 @@ class MulanVDM(_VDMBase):
         (notebook_utils.logits_to_embeddings), its KL term (_gumbel_kl_loss) and the schedule coefficients"""
         if not self.config.z_conditioning:
             raise NotImplementedError("reverse_ode hands the embedding to the score model (z_conditioning=True)")
+        if self.config.latent_type == 'gaussian':
+            raise NotImplementedError(
+                "ODE likelihood with latent_type='gaussian': the reference's apply_encoder returns (mu, var) there and "
+                "its ODE code (notebook_utils.logits_to_embeddings) cannot consume that")
         logits = self.apply_encoder(params, images_u8)
         emb, kl = ops.topk_hard(logits, self.config.latent_k)
         with torch.no_grad():

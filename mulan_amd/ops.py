@@ -2047,6 +2047,71 @@ def topk_embedding(logits, gnoise, k, tau=10.0):
     return TopKFn.apply(logits, gnoise, k, tau)
 
 
+class GumbelLatentFn(torch.autograd.Function):
+    """(embedding, kl_z) = straight-through Gumbel-softmax one-hot latent (ldm/model_mulan_velocity.py:68-92).
+    tau: 0-dim fp32 device tensor, read by the kernels when they run (a stream-ordered parameter under graph replay)."""
+
+    @staticmethod
+    def forward(ctx, logits, gnoise, tau):
+        logits, gnoise = _c(logits), _c(gnoise)
+        B, L = logits.shape
+        emb, soft = torch.empty_like(logits), torch.empty_like(logits)
+        kl = torch.empty(B, device=logits.device, dtype=torch.float32)
+        call("mulan_gumbel_latent_fwd", ptr(logits), ptr(gnoise), ptr(tau), ptr(emb), ptr(kl), ptr(soft), B, L, stream())
+        ctx.save_for_backward(logits, soft, tau)
+        return emb, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, demb, dkl):
+        logits, soft, tau = ctx.saved_tensors
+        B, L = logits.shape
+        demb = _c(demb) if demb is not None else torch.zeros_like(logits)
+        dkl = _c(dkl) if dkl is not None else torch.zeros(B, device=logits.device)
+        dl = torch.empty_like(logits)
+        call("mulan_gumbel_latent_bwd", ptr(logits), ptr(soft), ptr(tau), ptr(demb), ptr(dkl), ptr(dl), B, L, stream())
+        return dl, None, None
+
+
+def gumbel_embedding(logits, gnoise, tau):
+    """tau: 0-dim fp32 tensor on the logits' device"""
+    if not (torch.is_tensor(tau) and tau.dtype == torch.float32 and tau.numel() == 1 and tau.device == logits.device):
+        raise TypeError("gumbel_embedding: tau must be a one-element fp32 tensor on the logits' device")
+    return GumbelLatentFn.apply(logits, gnoise, _c(tau))
+
+
+class GaussianLatentFn(torch.autograd.Function):
+    """(embedding, kl_z) = mu + sqrt(softplus(s)) eps_z and its KL to N(0, I) (ldm/model_mulan_velocity.py:132-138 with
+    the softplus of UnetEncoderGaussian, ldm/model_mulan_epsilon.py:80)."""
+
+    @staticmethod
+    def forward(ctx, mu, s, eps_z):
+        mu, s, eps_z = _c(mu), _c(s), _c(eps_z)
+        B, L = mu.shape
+        emb = torch.empty_like(mu)
+        kl = torch.empty(B, device=mu.device, dtype=torch.float32)
+        call("mulan_gaussian_latent_fwd", ptr(mu), ptr(s), ptr(eps_z), ptr(emb), ptr(kl), B, L, stream())
+        ctx.save_for_backward(mu, s, eps_z)
+        return emb, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, demb, dkl):
+        mu, s, eps_z = ctx.saved_tensors
+        B, L = mu.shape
+        demb = _c(demb) if demb is not None else torch.zeros_like(mu)
+        dkl = _c(dkl) if dkl is not None else torch.zeros(B, device=mu.device)
+        dmu, ds = torch.empty_like(mu), torch.empty_like(s)
+        call("mulan_gaussian_latent_bwd", ptr(mu), ptr(s), ptr(eps_z), ptr(demb), ptr(dkl), ptr(dmu), ptr(ds), B, L,
+             stream())
+        return dmu, ds, None
+
+
+def gaussian_embedding(mu, s, eps_z):
+    """s: the pre-softplus head of the Gaussian encoder"""
+    return GaussianLatentFn.apply(mu, s, eps_z)
+
+
 # ----------------------------------------------------------------------------- optimiser
 def adamw_ema_step(p, g, m, v, ema, n_decay, lr, b1, b2, eps, wd, step, ema_rate, grad_scale=1.0, clip_norm=None, dyn=None):
     """one AdamW + EMA step on the flat buffers; clip_norm: optax.clip_by_global_norm in front (the factor is

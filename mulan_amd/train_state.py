@@ -31,7 +31,7 @@ def grad_ready_rank(path):
         return (net, pos, 0, mod)
     if sub == 'cond_proj' or mod in ('dense0', 'dense1'):
         return (net, 9, {'dense1': 1, 'dense0': 2}.get(mod, 0), '')          # after every block of the U-Net
-    if mod == 'dense_layer_final':
+    if mod in ('dense_layer_final', 'dense_layer_final_mu', 'dense_layer_final_sigma'):     # the latent head(s)
         return (net, 0, 0, mod)
     if mod == 'conv_out':
         return (net, 1, 0, mod)
