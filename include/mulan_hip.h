@@ -458,6 +458,17 @@ int mulan_decode_sample(const float* z0, const float* g0, unsigned char* out, si
  * path evaluates the bin of x inside mulan_qsample_fwd and never materialises the table. */
 int mulan_decode_logprobs(const float* z, const float* g0, float* out, size_t n, int g_per_sample,
                           mulan_stream_t stream);
+/* One step t -> s of the deterministic few-step samplers (not in the reference): DDIM with eta = 0 and
+ * DPM-Solver++(2M) on the probability-flow ODE, per element in lambda = -gamma / 2 (MuLAN's schedule is per sub-pixel):
+ * h = (g_t - g_s) / 2, x_hat = alpha_t z_t - sigma_t net (mode 0, velocity) | (z_t - sigma_t net) / alpha_t (mode 1,
+ * eps) | net (mode 2, plain VDM reparam_type 'input'); z_s = (sigma_s / sigma_t) z_t - alpha_s expm1(-h) D with
+ * D = x_hat (gprev = xprev = NULL: first order) or, given the previous step's gamma and x_hat, D = (1 + w) x_hat - w xprev,
+ * w = h / (2 h_p), h_p = (gprev - g_t) / 2 (2M; an element whose h_p is not finite and positive takes D = x_hat).
+ * x0 (nullable) receives x_hat, the next step's history.  gamma (gt, gs, gprev) per element (g_per_sample = 0) or one
+ * value per g_per_sample consecutive elements, as mulan_ancestral_step. */
+int mulan_fast_sampler_step(const float* zt, const float* net, const float* gt, const float* gs, const float* gprev,
+                            const float* xprev, float* zs, float* x0, size_t n, int mode, int g_per_sample,
+                            mulan_stream_t stream);
 /* out[r] = mean(x[r, :])  (VDM._get_score_model_gt, model_mulan_velocity.py:141-146) */
 int mulan_rowmean(const float* x, float* out, int rows, int cols, mulan_stream_t stream);
 

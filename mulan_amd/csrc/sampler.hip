@@ -145,3 +145,105 @@ MULAN_API int mulan_rowmean(const float* x, float* out, int rows, int cols, hipS
   hipLaunchKernelGGL(rowmean_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, out, rows, cols);
   MULAN_CHECK_LAUNCH();
 }
+
+// ---- deterministic few-step samplers: DDIM (eta = 0) and DPM-Solver++(2M) per element --------------------------------
+// MuLAN's forward process is diagonal, so lambda_i = -gamma_i / 2 is a change of variable per sub-pixel and the
+// DPM-Solver++ step holds coordinate by coordinate with the step size h = (g_t - g_s) / 2 of that coordinate:
+//   x_hat = alpha_t z_t - sigma_t net (mode 0, velocity) | (z_t - sigma_t net) / alpha_t (mode 1, eps) | net (mode 2)
+//   D = x_hat (first order), or with the previous step's (g_p, x_p): w = h / (2 h_p), D = (1 + w) x_hat - w x_p
+//   z_s = (sigma_s / sigma_t) z_t - alpha_s expm1(-h) D
+// An element whose h_p is not a finite positive number takes the first-order D (the history of a first step, a NaN
+// sentinel written by a replayed stepper, a pixel whose schedule did not move): one code path for both orders, so a
+// first-order step is the same bits whichever way it was asked for.  At g_s == g_t, sigma_s / sigma_t = 1 and
+// expm1(0) = 0: z_s == z_t exactly.
+namespace {
+
+__device__ __forceinline__ float fast_step_elem(float z, float nt, float g_t, float g_s, float g_p, float x_p, int mode,
+                                                bool second, float* xh_out) {
+  const float st2 = sigmoid_f(g_t), ss2 = sigmoid_f(g_s);
+  const float alpha_t = sqrtf(sigmoid_f(-g_t)), sigma_t = sqrtf(st2), alpha_s = sqrtf(sigmoid_f(-g_s));
+  float xh = nt;
+  if (mode == 0) xh = alpha_t * z - sigma_t * nt;
+  if (mode == 1) xh = (z - sigma_t * nt) / alpha_t;
+  *xh_out = xh;
+  const float h = 0.5f * (g_t - g_s);
+  float d = xh;
+  if (second) {
+    const float hp = 0.5f * (g_p - g_t);
+    if (hp > 0.f && hp < INFINITY) {
+      const float w = h / (2.f * hp);
+      d = (1.f + w) * xh - w * x_p;
+    }
+  }
+  return sqrtf(ss2 / st2) * z - alpha_s * expm1f(-h) * d;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void fast_sampler_step_kernel(const float* __restrict__ zt, const float* __restrict__ net,
+                                                                const float* __restrict__ gt, const float* __restrict__ gs,
+                                                                const float* __restrict__ gprev,
+                                                                const float* __restrict__ xprev, float* __restrict__ zs,
+                                                                float* __restrict__ x0, size_t n, int mode,
+                                                                int g_per_sample) {
+  const bool second = gprev != nullptr;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  if (VEC) {
+    // n % 4 == 0, every pointer 16-byte aligned, g_per_sample % 4 == 0: the four lanes of a float4 share one gamma
+    // per sample, or read a float4 of gamma per element
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n / 4; q += stride) {
+      const size_t i = q * 4;
+      const float4 z4 = reinterpret_cast<const float4*>(zt)[q], n4 = reinterpret_cast<const float4*>(net)[q];
+      float4 gt4, gs4, gp4 = make_float4(0.f, 0.f, 0.f, 0.f), xp4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (g_per_sample) {
+        const size_t gi = i / (size_t)g_per_sample;
+        gt4 = make_float4(gt[gi], gt[gi], gt[gi], gt[gi]);
+        gs4 = make_float4(gs[gi], gs[gi], gs[gi], gs[gi]);
+        if (second) gp4 = make_float4(gprev[gi], gprev[gi], gprev[gi], gprev[gi]);
+      } else {
+        gt4 = reinterpret_cast<const float4*>(gt)[q];
+        gs4 = reinterpret_cast<const float4*>(gs)[q];
+        if (second) gp4 = reinterpret_cast<const float4*>(gprev)[q];
+      }
+      if (second) xp4 = reinterpret_cast<const float4*>(xprev)[q];
+      float4 o, x;
+      o.x = fast_step_elem(z4.x, n4.x, gt4.x, gs4.x, gp4.x, xp4.x, mode, second, &x.x);
+      o.y = fast_step_elem(z4.y, n4.y, gt4.y, gs4.y, gp4.y, xp4.y, mode, second, &x.y);
+      o.z = fast_step_elem(z4.z, n4.z, gt4.z, gs4.z, gp4.z, xp4.z, mode, second, &x.z);
+      o.w = fast_step_elem(z4.w, n4.w, gt4.w, gs4.w, gp4.w, xp4.w, mode, second, &x.w);
+      reinterpret_cast<float4*>(zs)[q] = o;
+      if (x0) reinterpret_cast<float4*>(x0)[q] = x;
+    }
+  } else {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      const size_t gi = g_per_sample ? i / (size_t)g_per_sample : i;
+      float x;
+      zs[i] = fast_step_elem(zt[i], net[i], gt[gi], gs[gi], second ? gprev[gi] : 0.f, second ? xprev[i] : 0.f, mode,
+                             second, &x);
+      if (x0) x0[i] = x;
+    }
+  }
+}
+
+// memory-bound: one round of at most 2048 blocks (8 per CU), grid-stride beyond
+int grid_capped(size_t work) { return (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256); }
+
+bool aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+MULAN_API int mulan_fast_sampler_step(const float* zt, const float* net, const float* gt, const float* gs,
+                                      const float* gprev, const float* xprev, float* zs, float* x0, size_t n, int mode,
+                                      int g_per_sample, hipStream_t stream) {
+  if (n == 0 || mode < 0 || mode > 2 || g_per_sample < 0 || !zt || !net || !gt || !gs || !zs ||
+      (gprev == nullptr) != (xprev == nullptr) || (g_per_sample && n % (size_t)g_per_sample))
+    return (int)hipErrorInvalidValue;
+  const bool vec = n % 4 == 0 && (g_per_sample % 4) == 0 && aligned16(zt) && aligned16(net) && aligned16(zs) &&
+                   aligned16(x0) && aligned16(xprev) && (g_per_sample || (aligned16(gt) && aligned16(gs) && aligned16(gprev)));
+  if (vec)
+    hipLaunchKernelGGL(fast_sampler_step_kernel<true>, dim3(grid_capped(n / 4)), dim3(256), 0, stream, zt, net, gt, gs,
+                       gprev, xprev, zs, x0, n, mode, g_per_sample);
+  else
+    hipLaunchKernelGGL(fast_sampler_step_kernel<false>, dim3(grid_capped(n)), dim3(256), 0, stream, zt, net, gt, gs, gprev,
+                       xprev, zs, x0, n, mode, g_per_sample);
+  MULAN_CHECK_LAUNCH();
+}

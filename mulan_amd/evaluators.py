@@ -16,6 +16,7 @@ import torch.distributed as dist
 from . import checkpoint as ckpt_lib
 from . import data as dataset
 from . import parallel
+from . import sampling
 from .experiment import Experiment_VDM
 from .rng import PRNGKey
 
@@ -36,46 +37,63 @@ class Experiment_Colab(Experiment_VDM):
         self.rngs = {'sample': sample_rng}
 
     # ---- samplers of the notebook front end (ldm/notebook_utils.py:54-135) --------------------------------------
-    def _embedding_samples(self, embedding, rng, T):
-        """T ancestral steps of model.conditional_sample under a fixed [B, 50] embedding, then generate_x"""
-        from . import ops  # noqa: F401
-        B = embedding.shape[0]
+    def _embedding_samples(self, embedding, rng, T, sampler='ancestral'):
+        """T steps of `sampler` under a fixed [B, 50] embedding (ancestral: model.conditional_sample), then generate_x
+        (Experiment_VDM.draw_samples; z_1 ~ N(0, I) as the notebook draws it)"""
         rng = rng.fold_in(self.rank)
         rng, sample_rng = rng.split()
-        packer = self.state.param_packer("ema")
-        with torch.no_grad():
-            if packer is not None:
-                packer.refresh()
-            try:
-                z = sample_rng.normal((B, 3072), self.device)
-                conditioning = torch.zeros(B, dtype=torch.uint8, device=self.device)
-                coeffs = self.model.sample_coefficients(self.params, embedding)
-                step = self.model.reverse_stepper(self.params, B, self.device, embedding, conditioning, coeffs, T)
-                for i in range(T):
-                    z = step(i, z, rng)
-                samples = self.model.generate_x(self.params, z, rng=rng.fold_in(T))
-            finally:
-                if packer is not None:
-                    packer.invalidate()
+        samples, _ = self.draw_samples(self.params, embedding.shape[0], embedding, sample_rng, rng, rng.fold_in(T),
+                                       sampling.check_sampler(sampler), T)
         return parallel.all_gather_tensor(samples)
 
-    def sample_conditionally(self, embedding, T=1000):
-        """Experiment_Colab.sample_conditionally: an image grid sampled under one 50-dim k-hot embedding"""
-        from . import ops  # noqa: F401
+    @staticmethod
+    def _steps(T, sampler):
+        """T of the notebook samplers: 1000 ancestral steps by default, 25 for ddim / dpm2m (as p_sample)"""
+        if T is not None:
+            return T
+        return 1000 if sampling.check_sampler(sampler) == 'ancestral' else 25
+
+    def sample_conditionally(self, embedding, T=None, sampler='ancestral'):
+        """Experiment_Colab.sample_conditionally: an image grid sampled under one 50-dim k-hot embedding (sampler: see
+        Experiment_VDM.sample_fn; T is the step count, by default 1000 ancestral / 25 few-step)"""
         B = self.eval_iter.local
         emb = torch.as_tensor(embedding, dtype=torch.float32, device=self.device).reshape(1, -1)
         assert emb.shape[1] == 50
-        samples = self._embedding_samples(emb.expand(B, 50).contiguous(), self.rng, T)
+        samples = self._embedding_samples(emb.expand(B, 50).contiguous(), self.rng, self._steps(T, sampler), sampler)
         return ckpt_lib.generate_image_grids(samples).astype(np.uint8)
 
-    def sample_randomly(self, T=1000):
+    def sample_randomly(self, T=None, sampler='ancestral'):
         """Experiment_Colab.sample_randomly: every image under the hard top-15 embedding of its own random logits"""
         from . import ops
         B = self.eval_iter.local
         _, embeddings_rng = self.rng.fold_in(self.rank).split()
         emb, _ = ops.topk_hard(embeddings_rng.normal((B, 50), self.device), 15)
-        samples = self._embedding_samples(emb, self.rng, T)
+        samples = self._embedding_samples(emb, self.rng, self._steps(T, sampler), sampler)
         return ckpt_lib.generate_image_grids(samples).astype(np.uint8)
+
+    def sample_batches(self, keys, batch_size, embedding='deterministic', sampler='dpm2m', steps=25):
+        """uint8 [batch_size, 32, 32, 3] per key, each batch drawn from its key alone (the python -m ldm.sample CLI):
+        key.split(3) -> (prior z_1 ~ sigma_prior N(0, I), random embedding logits, per-step noise of the ancestral
+        sampler); generate_x with key.fold_in(steps).  embedding 'deterministic': model.deterministic_embedding (as
+        sample_fn); 'random': the hard top-15 of random normal logits (as sample_randomly).  The few-step samplers re-use
+        one stepper, re-targeted at every batch's context."""
+        from . import ops
+        sampling.check_sampler(sampler)
+        if embedding not in ('deterministic', 'random'):
+            raise ValueError(f"embedding must be 'deterministic' or 'random', got {embedding!r}")
+        mulan = hasattr(self.model, "deterministic_embedding")
+        if embedding == 'random' and not mulan:
+            raise ValueError("embedding='random' needs a MuLAN model (model_vdm.VDM has no latent embedding)")
+        out, stepper = [], None
+        for key in keys:
+            k_z, k_e, k_s = key.split(3)
+            emb = None
+            if embedding == 'random':
+                emb, _ = ops.topk_hard(k_e.normal((batch_size, 50), self.device), 15)
+            x, stepper = self.draw_samples(self.params, batch_size, emb, k_z, k_s, key.fold_in(steps), sampler, steps,
+                                           prior_scale=float(self.config.model.sigma_prior), stepper=stepper)
+            out.append(x)
+        return out
 
     def test(self, loader):
         """Experiment_Colab.test: mean of the eval scalars over a loader"""

@@ -21,6 +21,7 @@ from . import checkpoint as ckpt_lib
 from . import data as dataset
 from . import parallel
 from . import profiling
+from . import sampling
 from .model import VDMConfig, make_vdm, tree_leaves
 from .rng import PRNGKey
 from .train_state import TrainState, tree_leaves_in_layout
@@ -483,14 +484,18 @@ class Experiment(abc.ABC):
     def p_sample(self, params, T=None):
         """self.p_sample of the reference (ldm/experiment.py:96-102): sample_fn on a batch shaped like one eval
         micro-batch, samples of all ranks concatenated.  T: config.training.sample_timesteps, default 1000 like the
-        reference's hard-coded value; 0 disables sampling at evaluation points."""
+        reference's hard-coded value; 0 disables sampling at evaluation points.  config.training.sampler (optional, not in
+        the reference): 'ancestral' (the default), 'ddim' or 'dpm2m', which then run sample_timesteps steps (default 25)."""
+        sampler = sampling.check_sampler(self.config.training.get('sampler', 'ancestral'))
         if T is None:
-            T = int(self.config.training.get('sample_timesteps', 1000))
+            T = int(self.config.training.get('sample_timesteps', 1000 if sampler == 'ancestral' else 25))
         if T <= 0:
             return None
         if self._sample_dummy is None:
             self._sample_dummy = torch.empty((self.eval_iter.local, 32, 32, 3), dtype=torch.uint8, device=self.device)
-        return self.sample_fn(dummy_inputs=self._sample_dummy, rng=self._sample_rng, params=params, T=T)
+        if sampler == 'ancestral':
+            return self.sample_fn(dummy_inputs=self._sample_dummy, rng=self._sample_rng, params=params, T=T)
+        return self.sample_fn(dummy_inputs=self._sample_dummy, rng=self._sample_rng, params=params, T=T, sampler=sampler)
 
     def _write_samples(self, writer, step, params):
         samples = self.p_sample(params)
@@ -560,38 +565,72 @@ class Experiment_VDM(Experiment):
         metrics = {'scalars': scalar_dict, 'images': {'inputs': inputs['images']}}
         return bpd, metrics
 
-    def sample_fn(self, *, dummy_inputs, rng, params, T=1000, gather=True):
+    def sample_fn(self, *, dummy_inputs, rng, params, T=1000, gather=True, sampler='ancestral', t_grid=None):
         """Experiment_VDM.sample_fn (ldm/experiment_vdm.py:80-110): z_T ~ sigma_prior N(0, I), T ancestral steps
         (`model.sample`), `model.generate_x`; returns uint8 samples [B (* world), 32, 32, 3].  The noise stream is this
-        build's Philox, folded with the rank like the reference folds axis_index."""
+        build's Philox, folded with the rank like the reference folds axis_index.
+        sampler (not in the reference): 'ancestral' (the reference's loop), or the deterministic few-step samplers 'ddim' /
+        'dpm2m' (mulan_amd.sampling) over T uniform steps or the explicit t_grid (1 -> 0, strictly decreasing: it sets
+        the step count); generate_x then draws with rng.fold_in(N) like the ancestral loop with fold_in(T)."""
+        sampling.check_sampler(sampler)
+        if sampler == 'ancestral' and t_grid is not None:
+            raise ValueError("t_grid applies to the ddim / dpm2m samplers; the ancestral sampler runs T uniform steps")
+        grid = None if sampler == 'ancestral' else sampling.time_grid(None if t_grid is not None else T, t_grid)
+        N = T if grid is None else len(grid) - 1
         rng = rng.fold_in(self.rank)
         B = dummy_inputs.shape[0]
-        conditioning = torch.zeros(B, dtype=torch.uint8, device=self.device)
         rng, sample_rng = rng.split()
-        packer = None
+        samples, _ = self.draw_samples(params, B, None, sample_rng, rng, rng.fold_in(N), sampler, N, t_grid=grid,
+                                       prior_scale=float(self.config.model.sigma_prior))
+        return parallel.all_gather_tensor(samples) if gather else samples
+
+    def _packer_for(self, params):
         if params is self.state.ema_params:
-            packer = self.state.param_packer("ema")
-        elif params is self.state.params:
-            packer = self.state.param_packer("params")
+            return self.state.param_packer("ema")
+        if params is self.state.params:
+            return self.state.param_packer("params")
+        return None
+
+    def draw_samples(self, params, B, embedding, prior_rng, step_rng, decode_rng, sampler, steps, t_grid=None,
+                     prior_scale=1.0, stepper=None):
+        """One batch of B images, the loop every sampling entry point runs: z_1 = prior_scale * N(0, I) from prior_rng,
+        `steps` steps of `sampler` under `embedding` (MuLAN models; None: model.deterministic_embedding) with the per-step
+        noise of the ancestral sampler from step_rng (rng.fold_in(i) at step i), generate_x with decode_rng (needed by
+        sample_softmax).  The weights are packed once for the whole loop.  ancestral: the reverse step is a replayed HIP
+        graph (model.GraphedReverseStep); ddim / dpm2m (t_grid, if given, sets the step count): model.fast_sample, the
+        stepper re-used when one is given (re-targeted at this batch's context) and returned for the next batch.
+        -> (uint8 [B, 32, 32, 3], stepper or None)"""
+        packer = self._packer_for(params)
+        conditioning = torch.zeros(B, dtype=torch.uint8, device=self.device)
+        mulan = hasattr(self.model, "reverse_stepper")
         with torch.no_grad():
             if packer is not None:
-                packer.refresh()                     # weights are constant over the T steps: prepare them once
+                packer.refresh()                     # weights are constant over the steps: prepare them once
             try:
-                z = float(self.config.model.sigma_prior) * sample_rng.normal((B, 3072), self.device)
+                z = float(prior_scale) * prior_rng.normal((B, 3072), self.device)
+                if mulan and embedding is None:
+                    embedding = self.model.deterministic_embedding(B, self.device)
                 coeffs = None
-                if hasattr(self.model, "reverse_stepper"):
-                    # MuLAN models: the embedding of the sampler is fixed, so the schedule's coefficients are formed once,
-                    # and the reverse step is a replayed HIP graph (model.GraphedReverseStep; MULAN_SAMPLER_GRAPH=0: eager)
-                    emb = self.model.deterministic_embedding(B, self.device)
-                    coeffs = self.model.sample_coefficients(params, emb)
-                    step = self.model.reverse_stepper(params, B, self.device, emb, conditioning, coeffs, T)
-                    for i in range(T):
-                        z = step(i, z, rng)
+                if sampler == 'ancestral':
+                    if mulan:
+                        # MuLAN models: the embedding of the sampler is fixed, so the schedule's coefficients are formed
+                        # once, and the reverse step is a replayed HIP graph (MULAN_SAMPLER_GRAPH=0: eager)
+                        coeffs = self.model.sample_coefficients(params, embedding)
+                        step = self.model.reverse_stepper(params, B, self.device, embedding, conditioning, coeffs, steps)
+                        for i in range(steps):
+                            z = step(i, z, step_rng)
+                    else:
+                        for i in range(steps):
+                            z = self.model.sample(params, i, steps, z, conditioning, step_rng, coeffs)
                 else:
-                    for i in range(T):
-                        z = self.model.sample(params, i, T, z, conditioning, rng, coeffs)
-                samples = self.model.generate_x(params, z, coeffs, rng=rng.fold_in(T))
+                    ctx = self.model.fast_context(params, embedding if mulan else None, conditioning)
+                    if stepper is None:
+                        stepper = self.model.fast_stepper(params, B, self.device, ctx)
+                    z = self.model.fast_sample(params, z, ctx, sampler, None if t_grid is not None else steps, t_grid,
+                                               stepper=stepper)
+                    coeffs = ctx.get("coeffs")
+                samples = self.model.generate_x(params, z, coeffs, rng=decode_rng)
             finally:
                 if packer is not None:
                     packer.invalidate()
-        return parallel.all_gather_tensor(samples) if gather else samples
+        return samples, stepper

@@ -195,6 +195,99 @@ class GraphedReverseStep:
         return self.z_out.view(z.shape)
 
 
+def _check_fast_context(like, ctx):
+    """a stepper built for one context takes another only with the same keys and shapes (no broadcast of a [1, 50]
+    embedding over a stepper of B rows)"""
+    if set(like) != set(ctx):
+        raise ValueError(f"sampler context keys {sorted(ctx)} differ from the stepper's {sorted(like)}")
+    for k, v in ctx.items():
+        a, b = like[k], v
+        pairs = zip(a, b) if isinstance(a, tuple) else [(a, b)]
+        if isinstance(a, tuple) and (not isinstance(b, tuple) or len(a) != len(b)):
+            raise ValueError(f"sampler context {k!r}: expected {len(a)} tensors")
+        for x, y in pairs:
+            if (x is None) != (y is None) or (x is not None and tuple(x.shape) != tuple(y.shape)):
+                raise ValueError(f"sampler context {k!r}: shape {None if y is None else tuple(y.shape)} where the "
+                                 f"stepper was built for {None if x is None else tuple(x.shape)}")
+
+
+class EagerFastStep:
+    """The eager form of GraphedFastStep (MULAN_SAMPLER_GRAPH=0, or a failed capture): sampling.EagerStepper over the
+    model's network and schedule, reading the context through this object so that set_context() re-targets it at the
+    next batch like the replayed stepper."""
+
+    def __init__(self, model, params, B, device, ctx):
+        from . import sampling
+        self.ctx = ctx
+        times = lambda t: torch.full((B,), float(np.float32(t)), device=device, dtype=torch.float32)
+        gamma_fn = lambda t: model._fast_gamma(params, self.ctx, times(t))
+        net_fn = lambda z, t: model._fast_net(params, z.reshape(B, D), gamma_fn(t), self.ctx).view(z.shape)
+        self._make = lambda: sampling.EagerStepper(net_fn, gamma_fn, model._fast_mode())
+        self._step = self._make()
+
+    def set_context(self, ctx):
+        _check_fast_context(self.ctx, ctx)
+        self.ctx = ctx
+        self._step = self._make()             # no history and no cached gamma of the previous batch
+
+    def __call__(self, z, t, s, order):
+        return self._step(z, t, s, order)
+
+
+class GraphedFastStep:
+    """One step of the deterministic few-step samplers (DDIM / DPM-Solver++(2M), mulan_amd.sampling) captured as a HIP
+    graph and replayed N times.  What changes from step to step reaches the kernels through static buffers written
+    before each replay: z_t, the two times t, s and the history (the previous step's gamma and x_hat, copied from the
+    graph's outputs after each replay); a first-order step fills the previous gamma with NaN, which mulan_fast_sampler_step
+    reads as "no usable history" (the same code path as its NULL form, so the same bits).  The per-batch context (the
+    embedding and the schedule coefficients of the MuLAN models) sits in buffers of its own: set_context() re-targets the
+    graph at the next batch.  The replayed step is bit-identical to the eager one
+    (tests/test_gpu_fast_sampler.py::test_replayed_fast_step_equals_the_eager_step).  The weights must stay as they are
+    while the stepper lives (the caller holds the ParamPacker refresh)."""
+
+    def __init__(self, model, params, B, device, ctx):
+        self.B = B
+        f32 = dict(device=device, dtype=torch.float32)
+        self.ctx = {k: (None if v is None else tuple(c.detach().clone() for c in v) if isinstance(v, tuple)
+                        else v.detach().clone()) for k, v in ctx.items()}
+        self.z_in, self.x_prev = torch.zeros((B, D), **f32), torch.zeros((B, D), **f32)
+        self.t, self.s = torch.full((B,), 1.0, **f32), torch.full((B,), 0.5, **f32)
+        self.g_prev = torch.full(model._fast_gamma_shape(B), float("nan"), **f32)
+        run = lambda: model._fast_step(params, self.z_in, self.t, self.s, self.g_prev, self.x_prev, self.ctx)
+        with torch.no_grad():
+            for _ in range(2):         # eager first: every kernel configured, the allocator warm
+                run()
+            torch.cuda.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self.z_out, self.x_out, self.g_out = run()
+        self.has_history = False
+
+    def set_context(self, ctx):
+        _check_fast_context(self.ctx, ctx)
+        for k, v in ctx.items():
+            if isinstance(v, tuple):
+                for dst, src in zip(self.ctx[k], v):
+                    dst.copy_(src)
+            elif v is not None:
+                self.ctx[k].copy_(v)
+        self.has_history = False
+
+    def __call__(self, z, t, s, order):
+        if order == 2 and not self.has_history:
+            raise RuntimeError("a second-order step needs the history of a previous step")
+        self.z_in.copy_(z.reshape(self.B, D))
+        self.t.fill_(float(np.float32(t)))
+        self.s.fill_(float(np.float32(s)))
+        if order != 2:
+            self.g_prev.fill_(float("nan"))
+        self.graph.replay()
+        self.x_prev.copy_(self.x_out)
+        self.g_prev.copy_(self.g_out)
+        self.has_history = True
+        return self.z_out.view(z.shape)
+
+
 ODE_GRAPH = os.environ.get("MULAN_ODE_GRAPH", "1") == "1"      # A/B switch: 0 = every function evaluation issued eagerly
 
 
@@ -469,6 +562,50 @@ class _VDMBase:
     def __call__(self, params, *a, **kw):
         return self.apply(params, *a, **kw)
 
+    # ---- deterministic few-step samplers (mulan_amd.sampling; not in the reference) --------------------------------
+    # A model supplies _fast_gamma (gamma at the times of a [B] device tensor), _fast_net (the network output at z_t),
+    # _fast_mode (how mulan_fast_sampler_step reads that output) and _fast_gamma_shape.  ctx: the per-batch context
+    # (MuLAN: the embedding and the schedule coefficients; the plain VDM: the conditioning only).
+    def _fast_step(self, params, z, t, s, g_prev, x_prev, ctx):
+        """the device work of one step t -> s: (z_s, x_hat_t, gamma_t); g_prev / x_prev None: first order"""
+        g_t = self._fast_gamma(params, ctx, t)
+        g_s = self._fast_gamma(params, ctx, s)
+        net = self._fast_net(params, z, g_t, ctx)
+        z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, self._fast_mode(), g_prev, x_prev)
+        return z_s, x0, g_t
+
+    def fast_stepper(self, params, B, device, ctx, graph=None):
+        """-> step(z, t, s, order) of the few-step samplers: a replayed HIP graph (GraphedFastStep) by default
+        (MULAN_SAMPLER_GRAPH), eager where the capture fails (logged) or graph=False (EagerFastStep); both take the next
+        batch's context through set_context()"""
+        if graph is None:
+            graph = SAMPLER_GRAPH
+        if graph and torch.device(device).type == "cuda":
+            try:
+                return GraphedFastStep(self, params, B, device, ctx)
+            except Exception as e:      # noqa: BLE001  the replay is an optimisation: fall back loudly
+                import logging
+                logging.getLogger("mulan").warning("HIP-graph capture of the few-step sampler's step failed (%s: %s); "
+                                                   "sampling eagerly", type(e).__name__, e)
+        return EagerFastStep(self, params, B, device, ctx)
+
+    def fast_sample(self, params, z, ctx, sampler="dpm2m", steps=None, t_grid=None, graph=None, stepper=None):
+        """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m) over `steps` uniform steps or the explicit t_grid;
+        stepper: one from fast_stepper to re-use (its set_context re-targets it at this batch's ctx)"""
+        from . import sampling
+        grid = sampling.time_grid(steps, t_grid)
+        orders = sampling.step_orders(sampler, len(grid) - 1)
+        B = z.shape[0]
+        with torch.no_grad():
+            if stepper is None:
+                stepper = self.fast_stepper(params, B, z.device, ctx, graph)
+            elif not hasattr(stepper, "set_context"):
+                raise TypeError("fast_sample: a re-used stepper must take the batch's context (set_context): "
+                                f"{type(stepper).__name__} cannot be re-targeted")
+            else:
+                stepper.set_context(ctx)
+            return sampling.run(stepper, z.reshape(B, D).contiguous(), grid, orders)
+
 
 class MulanVDM(_VDMBase):
     """model_mulan_velocity.VDM / model_mulan_epsilon.VDM selected by `parameterization`."""
@@ -667,6 +804,34 @@ class MulanVDM(_VDMBase):
                 return ops.decode_sample(z_0.reshape(B, D), g_0, rng.v).view(B, 32, 32, 3)
             return ops.decode_argmax(z_0.reshape(B, D), g_0).view(B, 32, 32, 3)
 
+
+    # ---- few-step deterministic samplers (_VDMBase.fast_sample): the same embedding, conditioning and g_in as
+    # _reverse_step; the network output read as velocity_from_epsilon reads it in reverse_ode (mode 1 = eps_hat)
+    def fast_context(self, params, embedding, conditioning, coeffs=None):
+        """the per-batch context of fast_sample: the embedding, the conditioning and the schedule coefficients"""
+        B = embedding.shape[0]
+        if coeffs is None:
+            coeffs = self.sample_coefficients(params, embedding)
+        return dict(emb=embedding.contiguous(), cond=conditioning.reshape(B, 1).to(torch.float32).contiguous(),
+                    coeffs=tuple(coeffs))
+
+    def _fast_gamma(self, params, ctx, t):
+        return self._gamma_of(ctx["coeffs"], t)
+
+    def _fast_gamma_shape(self, B):
+        return (B, D)
+
+    def _fast_mode(self):
+        if self.parameterization == "velocity":
+            return 1 if self.config.velocity_from_epsilon else 0
+        return 1
+
+    def _fast_net(self, params, z, g_t, ctx):
+        cfg = self.config
+        B = z.shape[0]
+        cond = ctx["emb"] if cfg.z_conditioning else ctx["cond"]
+        g_in = g_t.view(B, HW, 3) if cfg.unet_type == 'ldm' else ops.rowmean(g_t)
+        return score_unet(params["score_model"], cfg, z.view(B, HW, 3), g_in, cond, _Drop(None, 0.0)).reshape(B, D)
 
     # ---- probability-flow ODE (ldm/model_mulan_velocity.py:51-53, 393-421; ldm/model_mulan_epsilon.py:459-478) ----
     def apply_encoder(self, params, images_u8):
@@ -881,6 +1046,27 @@ def _plain_reverse_ode(self, params, x, ctx, t, hutch=None, drift_out=None, div_
     return drift, ops.ode_div(gx.reshape(B, D), gt, gp, hutch, 2, div_out)
 
 
+def _plain_fast_context(self, params, embedding, conditioning, coeffs=None):
+    """fast_sample's context of model_vdm.VDM: the conditioning (there is no embedding and no coefficient)"""
+    B = conditioning.shape[0]
+    return dict(cond=conditioning.reshape(B, 1).to(torch.float32).contiguous())
+
+
+def _plain_fast_gamma(self, params, ctx, t):
+    return self._gamma(params, t)[0].contiguous()
+
+
+def _plain_fast_net(self, params, z, g_t, ctx):
+    """the network of _plain_sample: eps_hat (reparam_type 'noise') or x_hat ('input') at the per-sample gamma"""
+    B = z.shape[0]
+    return score_unet(params["score_model"], self.config, z.view(B, HW, 3), g_t, ctx["cond"], _Drop(None, 0.0)).reshape(B, D)
+
+
+PlainVDM.fast_context = _plain_fast_context
+PlainVDM._fast_gamma = _plain_fast_gamma
+PlainVDM._fast_gamma_shape = lambda self, B: (B,)
+PlainVDM._fast_mode = lambda self: 2 if self.config.reparam_type == 'input' else 1
+PlainVDM._fast_net = _plain_fast_net
 PlainVDM.ode_context_from_embedding = lambda self, params, emb: dict(emb=emb, kl=None, coeffs=None, logits=None)
 PlainVDM.apply_encoder = _plain_apply_encoder
 PlainVDM.ode_context = _plain_ode_context

@@ -2151,6 +2151,22 @@ def ancestral_step(zt, net, gt, gs, eps, mode):
     return zs
 
 
+def fast_sampler_step(zt, net, gt, gs, mode, gprev=None, xprev=None, x0=True):
+    """one deterministic step z_t -> z_s of DDIM (gprev = xprev = None) or DPM-Solver++(2M) (mulan_fast_sampler_step);
+    mode 0: net is the velocity, 1: eps_hat, 2: x_hat; gt / gs / gprev per element ([B,3072]) or per sample ([B]).
+    Returns (z_s, x_hat_t) (x_hat_t None when x0=False)"""
+    if (gprev is None) != (xprev is None):
+        raise ValueError("fast_sampler_step: gprev and xprev go together (both None: first order)")
+    zt, net, gt, gs = _c(zt), _c(net), _c(gt), _c(gs)
+    gprev, xprev = (None, None) if gprev is None else (_c(gprev), _c(xprev))
+    zs = torch.empty_like(zt)
+    xh = torch.empty_like(zt) if x0 else None
+    per = zt.numel() // gt.numel()
+    call("mulan_fast_sampler_step", ptr(zt), ptr(net), ptr(gt), ptr(gs), ptr(gprev), ptr(xprev), ptr(zs), ptr(xh),
+         zt.numel(), int(mode), 0 if per == 1 else per, stream())
+    return zs, xh
+
+
 def decode_argmax(z0, g0):
     """uint8 argmax over the 256 decoder bins at z_0 / sqrt(1 - sigmoid(g_0)) (VDM.generate_x, sample_softmax=False)"""
     z0, g0 = _c(z0), _c(g0)
