@@ -205,7 +205,8 @@ __global__ void noise_kernel(float* __restrict__ out, size_t n, unsigned long lo
         if (kind == 0) {
           v = u;
         } else if (kind == 3) {
-          v = -logf(-logf(u + 2.98023223876953125e-08f));                   // u in (0, 1)
+          // u in (0, 1): for the largest u the sum is a tie that rounds to 1.0f, whose Gumbel is +inf
+          v = -logf(-logf(fminf(u + 2.98023223876953125e-08f, 0.99999994f)));
         } else {
           const float p = plo + (phi - plo) * (u + 2.98023223876953125e-08f);
           v = fminf(fmaxf(1.41421356237309505f * erfinvf(2.f * p - 1.f), lo), hi);

@@ -16,6 +16,22 @@ struct AdamArgs {
   const float* dyn;          // optional [3] on the device: lr, 1 - b1^t, 1 - b2^t (stream-ordered: graph replay)
 };
 
+// One element's update, the only arithmetic of the step.  Left to the compiler, a * b + c * d contracts to
+// fma(a, b, c * d) in one instantiation of the kernel and to fma(c, d, a * b) in another (and to neither in the scalar
+// tail), so the variants below differed in the last bit of p, m and v.  The roundings are therefore spelled out, in the
+// form the shipped instantiation had, and contraction is off: every variant and the tail give the same bits.
+__device__ __forceinline__ void adamw_ema_update(const AdamArgs& a, float omb1, float omb2, float ome, bool decay,
+                                                 float g, float& p, float& m, float& v, float& e) {
+#pragma clang fp contract(off)
+  const float gk = g * a.gscale;
+  m = __builtin_fmaf(a.b1, m, omb1 * gk);
+  v = __builtin_fmaf(a.b2, v, (omb2 * gk) * gk);
+  float up = (m / a.bc1) / (sqrtf(v / a.bc2) + a.eps);
+  if (decay) up = __builtin_fmaf(a.wd, p, up);
+  p = __builtin_fmaf(-a.lr, up, p);
+  e = __builtin_fmaf(ome, p - e, e);
+}
+
 // U float4 per array and thread in flight (U = 2: 10 loads of 16 B before the first use); NT: non-temporal loads and
 // stores (every byte is touched once per step; the arrays are 4 x 142 MB + the gradient, nothing of it is reused
 // before the next step's weight packing reads p)
@@ -51,13 +67,9 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(AdamArgs a) {
       const size_t i = q << 2;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float gk = g[u][k] * a.gscale;
-        m[u][k] = a.b1 * m[u][k] + omb1 * gk;
-        v[u][k] = a.b2 * v[u][k] + omb2 * gk * gk;
-        float up = (m[u][k] / a.bc1) / (sqrtf(v[u][k] / a.bc2) + a.eps);
-        if (i + k < a.n_decay) up += a.wd * p[u][k];
-        p[u][k] -= a.lr * up;
-        e[u][k] += ome * (p[u][k] - e[u][k]);
+        float pk = p[u][k], mk = m[u][k], vk = v[u][k], ek = e[u][k];
+        adamw_ema_update(a, omb1, omb2, ome, i + k < a.n_decay, g[u][k], pk, mk, vk, ek);
+        p[u][k] = pk; m[u][k] = mk; v[u][k] = vk; e[u][k] = ek;
       }
       st(a.p + i, p[u]); st(a.m + i, m[u]); st(a.v + i, v[u]); st(a.ema + i, e[u]);
     }
@@ -65,15 +77,9 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(AdamArgs a) {
   // tail (n not a multiple of 4)
   if (blockIdx.x == 0) {
     for (size_t i = (n4 << 2) + threadIdx.x; i < a.n; i += blockDim.x) {
-      const float gk = a.g[i] * a.gscale;
-      const float m = a.b1 * a.m[i] + omb1 * gk;
-      const float v = a.b2 * a.v[i] + omb2 * gk * gk;
-      float u = (m / a.bc1) / (sqrtf(v / a.bc2) + a.eps);
-      float p = a.p[i];
-      if (i < a.n_decay) u += a.wd * p;
-      p -= a.lr * u;
-      a.p[i] = p; a.m[i] = m; a.v[i] = v;
-      a.ema[i] += ome * (p - a.ema[i]);
+      float p = a.p[i], m = a.m[i], v = a.v[i], e = a.ema[i];
+      adamw_ema_update(a, omb1, omb2, ome, i < a.n_decay, a.g[i], p, m, v, e);
+      a.p[i] = p; a.m[i] = m; a.v[i] = v; a.ema[i] = e;
     }
   }
 }

@@ -47,8 +47,8 @@ __global__ void decode_argmax_kernel(const float* __restrict__ z0, const float* 
         const Philox4 r = philox4x32_10(seed, offset + (unsigned long long)i * 64ull + j4, 0ull);
         const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          gum[e] = -logf(-logf(((float)(w[e] >> 8) + 0.5f) * 5.9604644775390625e-08f));
+        for (int e = 0; e < 4; ++e)   // (2^24 - 1) + 0.5 is a tie that rounds to 2^24: u = 1.0f, whose Gumbel is +inf
+          gum[e] = -logf(-logf(fminf(((float)(w[e] >> 8) + 0.5f) * 5.9604644775390625e-08f, 0.99999994f)));
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
