@@ -3,6 +3,8 @@
 Each Function's forward and backward are launches of hand-written HIP kernels through
 `mulan_amd.lib`; torch supplies device buffers, the current stream and the autograd tape only.
 Shapes: images are [B, 1024, C] (NHWC with H = W = 32 flattened), matrices row-major, all fp32.
+By-products that one node leaves on a tensor for the next (maxima, statistics, channel sums, planes ...) go through
+_leave / _left / _carry below; DESIGN.md section 2 ("By-products travel with the tensor") lists the tags.
 """
 import ctypes
 import math
@@ -154,28 +156,68 @@ def absmax_rows(x):
     return out
 
 
+# ----------------------------------------------------------------------------- by-products carried on tensors
+# What a kernel computed on the side travels to the next autograd node as a Python attribute of the tensor it describes
+# (DESIGN.md section 2).  Every tag is stored as payload + (version of the tensor when it was left,): an in-place write to
+# the tensor makes it stale.  Shape and compatibility checks differ per consumer and stay with the reader.
+def _leave(t, tag, *payload):
+    """leaves `payload` on t under the attribute `tag`, stamped with t's version; returns t.  An object that cannot take
+    an attribute goes without (its consumer then takes its own pass)."""
+    try:
+        setattr(t, tag, payload + (t._version,))
+    except (AttributeError, RuntimeError):
+        pass
+    return t
+
+
+def _payload(t, tag):
+    """the payload tuple left on t under `tag`, or None: t is None, nothing was left, or t was written to since"""
+    c = getattr(t, tag, None) if t is not None else None
+    return c[:-1] if (c is not None and c[-1] == t._version) else None
+
+
+def _left(t, tag):
+    """what _leave(t, tag, ...) left, if still valid: the bare value of a single payload, the tuple of several, True
+    for a tag without payload; else None"""
+    p = _payload(t, tag)
+    if p is None:
+        return None
+    return p[0] if len(p) == 1 else (p if p else True)
+
+
+# What an alias or a view of the same numbers may keep: `_absmax` (per-image maxima do not depend on how the trailing
+# dimensions are folded as long as dim 0 stays the batch) and `_gnstats` (per image, row tile and channel quad: a view
+# folded otherwise fails the reader's shape check).  `_colsum` describes the numbers too, but no alias site hands a
+# gradient on.  The other tags are not about the numbers but about one tensor's place in the graph -- a gradient sink
+# (`_bias_sink`, `_bias_twin`, `_biasdone`, `_biasgrad`), a layout bound to the shape (`_colsum_parts`, `_planes`,
+# `_grad_planes`) or a promise of the producing node (`_accepts_grad_planes`) -- and never move to another object.
+_VIEW_TAGS = ("_absmax", "_gnstats")
+
+
+def _carry(src, dst, tags=_VIEW_TAGS):
+    """re-stamps what is still valid of `tags` on src onto dst, an alias or view of src (a new Python object, which would
+    lose them); returns dst"""
+    for tag in tags:
+        p = _payload(src, tag)
+        if p is not None and not (tag == "_absmax" and p[0].shape[0] != dst.shape[0]):
+            _leave(dst, tag, *p)
+    return dst
+
+
 def cached_absmax(x):
     """maxima a producer kernel (GroupNormFn) or an earlier consumer left on the tensor, if still valid; else a pass
     over x, remembered on the tensor for its other consumers (a gradient that feeds a convolution and a 1x1 layer)"""
-    c = getattr(x, "_absmax", None)
-    if c is not None and c[1] == x._version and c[0].shape[0] == x.shape[0]:
-        return c[0]
+    m = _left(x, "_absmax")
+    if m is not None and m.shape[0] == x.shape[0]:
+        return m
     m = absmax_rows(x)
-    try:
-        x._absmax = (m, x._version)
-    except (AttributeError, RuntimeError):
-        pass
+    _leave(x, "_absmax", m)
     return m
 
 
 def view_keep_absmax(x, *shape):
-    """x.view(shape) that keeps the maxima found on x (a view is a new Python object and would lose them; the
-    per-image maxima do not depend on how the trailing dimensions are folded as long as dim 0 stays the batch)"""
-    v = x.view(*shape)
-    c = getattr(x, "_absmax", None)
-    if c is not None and c[1] == x._version and v.shape[0] == c[0].shape[0]:
-        v._absmax = (c[0], v._version)
-    return v
+    """x.view(shape) that keeps the maxima found on x"""
+    return _carry(x, x.view(*shape), tags=("_absmax",))
 
 
 TEE_COLSUM = _os.environ.get("MULAN_TEE_COLSUM", "1") == "1"     # A/B switch: 0 = the bias gradient takes its own pass
@@ -188,13 +230,7 @@ class TeeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        a, b = x.view_as(x), x.view_as(x)
-        for v in (a, b):
-            for tag in ("_absmax", "_gnstats"):     # what the producer left on x stays valid for the aliases
-                c = getattr(x, tag, None)
-                if c is not None and c[1] == x._version:
-                    setattr(v, tag, (c[0], v._version))
-        return a, b
+        return _carry(x, x.view_as(x)), _carry(x, x.view_as(x))
 
     @staticmethod
     @once_differentiable
@@ -213,11 +249,10 @@ class TeeFn(torch.autograd.Function):
             parts = torch.empty((ga.shape[0] * MAX_PARTS, N), device=ga.device, dtype=torch.float32)
             call("mulan_add_absmax_rows_colsum", ptr(ga), ptr(gb), ptr(out), ptr(m), ptr(parts), ga.shape[0],
                  ga.numel() // ga.shape[0], N, stream())
-            out._colsum_parts = (parts, out._version)
+            _leave(out, "_colsum_parts", parts)
         else:
             call("mulan_add_absmax_rows", ptr(ga), ptr(gb), ptr(out), ptr(m), ga.shape[0], ga.numel() // ga.shape[0], stream())
-        out._absmax = (m, out._version)
-        return out
+        return _leave(out, "_absmax", m)
 
 
 # The gradient sum of a block output with two consumers inside the GroupNorm backward kernel of the first consumer
@@ -270,12 +305,7 @@ class MailFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, box):
         ctx.box = box
-        y = x.view_as(x)
-        for tag in ("_absmax", "_gnstats"):
-            c = getattr(x, tag, None)
-            if c is not None and c[1] == x._version:
-                setattr(y, tag, (c[0], y._version))
-        return y
+        return _carry(x, x.view_as(x))
 
     @staticmethod
     @once_differentiable
@@ -425,7 +455,7 @@ def conv3x3_raw(x, w, bias=None, cbias=None, res=None, xmax=None, planes=False, 
                lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(x), ptr(xmax), ptr(wp), ptr(wmax), ptr(bias), ptr(cbias), mode,
                             ptr(res), ptr(y), ptr(xs), ptr(ymax), _alone(), B, H, W, C, N, stream()))
         if ymax is not None:
-            y._absmax = (ymax, y._version)
+            _leave(y, "_absmax", ymax)
         if planes:
             return y, xs
     else:
@@ -455,7 +485,7 @@ def conv3x3_dgrad_raw(dy, w, dymax=None, planes=False, wmax=None, want_max=False
                    lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(dy), ptr(dymax), ptr(wp), ptr(wmax), None, None, 0, None,
                                 ptr(dx), ptr(dys), ptr(dxmax), _alone(), B, H, W, N, C, stream()))
             if dxmax is not None:
-                dx._absmax = (dxmax, dx._version)
+                _leave(dx, "_absmax", dxmax)
             if planes:
                 return dx, dys
         else:
@@ -485,7 +515,7 @@ def conv3x3_dgrad_planes_raw(dys, dymax, w, wmax=None, want_max=False):
            lambda: call("mulan_conv3x3_fwd_f16x3_planes_in_stats", ptr(dys), ptr(dymax), ptr(wp), ptr(wmax), None, None, 0,
                         None, ptr(dx), ptr(dxmax), None, alone, B, H, W, N, C, stream()))
     if dxmax is not None:
-        dx._absmax = (dxmax, dx._version)
+        _leave(dx, "_absmax", dxmax)
     return dx
 
 
@@ -501,18 +531,11 @@ _NAN = {}
 def _planes_only_grad(shape, device, planes, bound):
     """The stand-in autograd carries for a gradient that exists only as split planes: a NaN scalar expanded to the
     gradient's shape (4 bytes; anything that consumed it as numbers would turn NaN at once -- loud, not silent) with the
-    real content attached as `_grad_planes = (planes, bound maxima, version)`"""
+    real content left on it as `_grad_planes` (planes, bound maxima)"""
     n = _NAN.get(device)
     if n is None:
         n = _NAN[device] = torch.full((1,), float("nan"), device=device, dtype=torch.float32)
-    g = n.expand(*shape)
-    g._grad_planes = (planes, bound, g._version)
-    return g
-
-
-def _grad_planes_of(dy):
-    gp = getattr(dy, "_grad_planes", None)
-    return gp if (gp is not None and gp[2] == dy._version) else None
+    return _leave(n.expand(*shape), "_grad_planes", planes, bound)
 
 
 def _gv(t):
@@ -679,10 +702,7 @@ class Conv3x3Fn(torch.autograd.Function):
         ctx.has = (bias is not None, None if cbias is None else cbias.dim(), res is not None)
         ctx.gv = (_gv(w), _gv(bias))
         if ctx.gv[1] is not None and ctx.needs_input_grad[2]:
-            # A GroupNorm that consumes y writes this bias' gradient (the channel sums of the dy it produces) from inside
-            # its backward kernel; `twin`: the bias of the shortcut layer whose output is `res` sees the same gradient.
-            twin = getattr(res, "_bias_twin", None) if res is not None else None
-            y._bias_sink = (ctx.gv[1], twin[0] if (twin is not None and twin[1] == res._version) else None, y._version)
+            _leave_bias_sink(y, ctx.gv[1], res)
         return y
 
     @staticmethod
@@ -691,53 +711,60 @@ class Conv3x3Fn(torch.autograd.Function):
         return _conv3x3_backward(ctx, dy)
 
 
+def _leave_bias_sink(y, gvb, res):
+    """A GroupNorm that consumes y writes the gradient of the bias behind y (gvb: its sink; the channel sums of the dy it
+    produces) from inside its backward kernel; the twin: the bias of the shortcut layer whose output is `res` sees the
+    same gradient."""
+    _leave(y, "_bias_sink", gvb, _left(res, "_bias_twin"))
+
+
+def _bias_sink_of(x1, C1):
+    """(sink, twin sink or None) left by the convolution that produced x1 (_leave_bias_sink), or None"""
+    bs = _left(x1, "_bias_sink")
+    return bs if (bs is not None and bs[0].numel() == C1) else None
+
+
 def _conv3x3_backward(ctx, dy):
     """backward of y = conv3x3(x, w) + bias + cbias + res -> (dx, dw, dbias, dcbias, dres); ctx: the Conv3x3Fn context
     or the stand-in GnConv3x3Fn builds (saved_tensors = (x or its planes, w), planes, xmax, wmax, has, gv,
     needs_input_grad[0..4])"""
-    if True:
-        x, w = ctx.saved_tensors
-        has_bias, cb_dim, has_res = ctx.has
-        gvw, gvb = ctx.gv
-        B, N = dy.shape[0], dy.shape[-1]
-        want_max = bool(getattr(ctx, "want_dx_max", False))
+    x, w = ctx.saved_tensors
+    has_bias, cb_dim, has_res = ctx.has
+    gvw, gvb = ctx.gv
+    B, N = dy.shape[0], dy.shape[-1]
+    want_max = bool(getattr(ctx, "want_dx_max", False))
 
-        def wgrad_from_planes(dys, dymax):
-            if _side_ok(gvw):
-                dw_, xmax = _fresh(gvw), ctx.xmax
-                _on_side(lambda: conv3x3_wgrad_planes_raw(x, xmax, dys, dymax, B, w.shape[2], N, out=dw_),
-                         (x, xmax, dys, dymax))
-                return dw_
-            return conv3x3_wgrad_planes_raw(x, ctx.xmax, dys, dymax, B, w.shape[2], N,
-                                            out=_fresh(gvw) if gvw is not None else None)
+    def wgrad_from_planes(dys, dymax):
+        if _side_ok(gvw):
+            dw_, xmax = _fresh(gvw), ctx.xmax
+            _on_side(lambda: conv3x3_wgrad_planes_raw(x, xmax, dys, dymax, B, w.shape[2], N, out=dw_),
+                     (x, xmax, dys, dymax))
+            return dw_
+        return conv3x3_wgrad_planes_raw(x, ctx.xmax, dys, dymax, B, w.shape[2], N,
+                                        out=_fresh(gvw) if gvw is not None else None)
 
-        gp = _grad_planes_of(dy)
-        if gp is not None:
-            # dy exists only as split planes (written by the GroupNorm backward behind this convolution,
-            # mulan_groupnorm_bwd_fused_planes): the plane-fed convolution kernel forms dx, the weight-gradient kernel
-            # reads the same planes, bias / FiLM gradients come from the channel sums that kernel left.  Nothing here
-            # may read dy's numbers (the tensor is a NaN stand-in).
-            assert not has_res and cb_dim != 3 and getattr(dy, "_colsum", None) is not None, "planes-only gradient misrouted"
-            dys, dymax = gp[0], gp[1]
-            dx = conv3x3_dgrad_planes_raw(dys, dymax, w, wmax=ctx.wmax, want_max=want_max)
-            dw = wgrad_from_planes(dys, dymax) if ctx.needs_input_grad[1] else None
-        else:
-            nan = _NAN.get(dy.device)
-            if nan is not None and dy.numel() > 1 and dy.data_ptr() == nan.data_ptr() and all(s == 0 for s in dy.stride()):
-                # the NaN stand-in of _planes_only_grad without (valid) planes: autograd handed on another tensor object than
-                # the GroupNorm backward returned (a tensor hook, retain_grad or an accumulation on conv1's output)
-                raise RuntimeError("planes-only gradient arrived without its planes: hooks / retain_grad / a second consumer "
-                                   "on the output of a ResnetBlock's conv1 are not supported with MULAN_GRAD_PLANES=1")
-            dy = _c(dy)
-            dymax = cached_absmax(dy) if (CONV_MODE == "f16x3" and N % 4 == 0) else None   # shared by dgrad and wgrad
-        if gp is not None:
-            pass
-        elif ctx.planes:                # x is the plane tensor here
+    gp = _left(dy, "_grad_planes")
+    if gp is not None:
+        # dy exists only as split planes (written by the GroupNorm backward behind this convolution,
+        # mulan_groupnorm_bwd_fused_planes): the plane-fed convolution kernel forms dx, the weight-gradient kernel
+        # reads the same planes, bias / FiLM gradients come from the channel sums that kernel left.  Nothing here
+        # may read dy's numbers (the tensor is a NaN stand-in).
+        assert not has_res and cb_dim != 3 and _left(dy, "_colsum") is not None, "planes-only gradient misrouted"
+        dys, dymax = gp
+        dx = conv3x3_dgrad_planes_raw(dys, dymax, w, wmax=ctx.wmax, want_max=want_max)
+        dw = wgrad_from_planes(dys, dymax) if ctx.needs_input_grad[1] else None
+    else:
+        nan = _NAN.get(dy.device)
+        if nan is not None and dy.numel() > 1 and dy.data_ptr() == nan.data_ptr() and all(s == 0 for s in dy.stride()):
+            # the NaN stand-in of _planes_only_grad without (valid) planes: autograd handed on another tensor object than
+            # the GroupNorm backward returned (a tensor hook, retain_grad or an accumulation on conv1's output)
+            raise RuntimeError("planes-only gradient arrived without its planes: hooks / retain_grad / a second consumer "
+                               "on the output of a ResnetBlock's conv1 are not supported with MULAN_GRAD_PLANES=1")
+        dy = _c(dy)
+        dymax = cached_absmax(dy) if (CONV_MODE == "f16x3" and N % 4 == 0) else None   # shared by dgrad and wgrad
+        if ctx.planes:                  # x is the plane tensor here
             dx, dys = conv3x3_dgrad_raw(dy, w, dymax=dymax, planes=True, wmax=ctx.wmax, want_max=want_max)
-            try:       # the shortcut layer that shares this dy takes its weight gradient from the same planes
-                dy._planes = (dys, dymax, dy._version)
-            except (AttributeError, RuntimeError):
-                pass
+            _leave(dy, "_planes", dys, dymax)   # the shortcut layer that shares this dy takes its weight gradient from them
             dw = wgrad_from_planes(dys, dymax)
         else:
             dx = (conv3x3_dgrad_raw(dy, w, dymax=dymax, wmax=ctx.wmax, want_max=want_max)
@@ -750,39 +777,33 @@ def _conv3x3_backward(ctx, dy):
                 else:
                     dw = conv3x3_wgrad_raw(x, dy, out=_fresh(gvw) if gvw is not None else None, xmax=ctx.xmax,
                                            dymax=dymax)
-        dbias = dcb = None
-        per_sample = None
-        parts = getattr(dy, "_colsum_parts", None)         # left by TeeFn.backward's add: 16 partial column sums per image
-        if parts is not None and not (parts[1] == dy._version and parts[0].shape[1] == N):
-            parts = None
-        if parts is not None and has_bias and ctx.needs_input_grad[2] and not (cb_dim == 2 and ctx.needs_input_grad[3]):
-            dbias = colsum_raw(parts[0], 1, parts[0].shape[0], N, out=_fresh(gvb).view(1, N) if gvb is not None else None).view(N)
-            try:
-                dy._biasgrad = (dbias.view(N), dy._version, None)
-            except (AttributeError, RuntimeError):
-                pass
-        elif (has_bias and ctx.needs_input_grad[2]) or (cb_dim == 2 and ctx.needs_input_grad[3]):
-            cs = getattr(dy, "_colsum", None)              # left by the GroupNorm backward that produced dy
-            per_sample = cs[0] if (cs is not None and cs[1] == dy._version and cs[0].shape == (B, N)) \
-                else colsum_raw(dy, B, HW, N)              # [B,N]
-        if dbias is None and has_bias and ctx.needs_input_grad[2]:
-            done = getattr(dy, "_biasdone", None)          # the GroupNorm backward already summed it into the sink
-            twin = None
-            if (done is not None and done[2] == dy._version and gvb is not None and
-                    done[0].data_ptr() == gvb.data_ptr()):
-                dbias, twin = _fresh(gvb), done[1]
-            else:
-                dbias = colsum_raw(per_sample, 1, B, N, out=_fresh(gvb).view(1, N) if gvb is not None else None,
-                                   ld=per_sample.stride(0)).view(N)
-            try:       # the shortcut layer that shares this dy (nin_shortcut + bias) needs the very same column sum
-                dy._biasgrad = (dbias.view(N), dy._version, twin)   # (a separate view: autograd adopts `dbias` itself)
-            except (AttributeError, RuntimeError):
-                pass
-        if cb_dim is not None and ctx.needs_input_grad[3]:
-            dcb = per_sample if cb_dim == 2 else dy
-        dres = dy if (has_res and ctx.needs_input_grad[4]) else None
-        assert gp is None or (dres is None and dcb is not dy)
-        return dx, dw, dbias, dcb, dres
+    dbias = dcb = None
+    per_sample = None
+    parts = _left(dy, "_colsum_parts")                 # left by TeeFn.backward's add: 16 partial column sums per image
+    if parts is not None and parts.shape[1] != N:
+        parts = None
+    if parts is not None and has_bias and ctx.needs_input_grad[2] and not (cb_dim == 2 and ctx.needs_input_grad[3]):
+        dbias = colsum_raw(parts, 1, parts.shape[0], N, out=_fresh(gvb).view(1, N) if gvb is not None else None).view(N)
+        _leave(dy, "_biasgrad", dbias.view(N), None)
+    elif (has_bias and ctx.needs_input_grad[2]) or (cb_dim == 2 and ctx.needs_input_grad[3]):
+        cs = _left(dy, "_colsum")                      # left by the GroupNorm backward that produced dy
+        per_sample = cs if (cs is not None and cs.shape == (B, N)) else colsum_raw(dy, B, HW, N)    # [B,N]
+    if dbias is None and has_bias and ctx.needs_input_grad[2]:
+        done = _left(dy, "_biasdone")                  # the GroupNorm backward already summed it into the sink
+        twin = None
+        if done is not None and gvb is not None and done[0].data_ptr() == gvb.data_ptr():
+            dbias, twin = _fresh(gvb), done[1]
+        else:
+            dbias = colsum_raw(per_sample, 1, B, N, out=_fresh(gvb).view(1, N) if gvb is not None else None,
+                               ld=per_sample.stride(0)).view(N)
+        # the shortcut layer that shares this dy (nin_shortcut + bias) needs the very same column sum; twin: the sink it
+        # was written into as well (a separate view: autograd adopts `dbias` itself)
+        _leave(dy, "_biasgrad", dbias.view(N), twin)
+    if cb_dim is not None and ctx.needs_input_grad[3]:
+        dcb = per_sample if cb_dim == 2 else dy
+    dres = dy if (has_res and ctx.needs_input_grad[4]) else None
+    assert gp is None or (dres is None and dcb is not dy)
+    return dx, dw, dbias, dcb, dres
 
 
 def conv3x3(x, w, bias=None, cbias=None, res=None):
@@ -801,17 +822,17 @@ def _tag_bias_twin(y, gvb, wanted):
     """A dense layer whose output becomes the residual input of a 3x3 convolution (nin_shortcut, ldm/model_vdm.py:652-656)
     has the same bias gradient as that convolution: the convolution passes this sink on (Conv3x3Fn.forward)."""
     if gvb is not None and wanted:
-        y._bias_twin = (gvb, y._version)
+        _leave(y, "_bias_twin", gvb)
 
 
 def _dense_bias_grad(dy, M, N, gvb):
     """sum of dy over all rows; re-used from the convolution that consumed the same dy when there is one"""
     out = _fresh(gvb) if gvb is not None else None
-    c = getattr(dy, "_biasgrad", None)
-    if c is not None and c[1] == dy._version and c[0].numel() == N:
+    c = _left(dy, "_biasgrad")              # (the column sum, the twin sink it went to as well or None)
+    if c is not None and c[0].numel() == N:
         if out is None:
             return c[0].view(N)
-        if not (len(c) > 2 and c[2] is not None and c[2].data_ptr() == out.data_ptr()):   # else: written there already
+        if not (c[1] is not None and c[1].data_ptr() == out.data_ptr()):   # else: written there already
             out.view(N).copy_(c[0].view(N))
         return out.view(N)
     return colsum_raw(dy.reshape(M, N), 1, M, N, out=out.view(1, N) if out is not None else None).view(N)
@@ -1076,9 +1097,9 @@ class Linear2Fn(torch.autograd.Function):
         gvw, gvb = ctx.gv
         if ctx.needs_input_grad[2]:
             dw = _fresh(gvw) if gvw is not None else torch.empty_like(w)
-            pl = getattr(dy, "_planes", None)
+            pl = _left(dy, "_planes")       # (planes of dy, its maxima) left by the convolution that consumed the same dy
             x32 = getattr(ctx, "x32", None)
-            if x32 is not None and pl is not None and pl[2] == dy._version and pl[0].numel() == M * N * 4:
+            if x32 is not None and pl is not None and pl[0].numel() == M * N * 4:
                 B_ = M // HW
                 x1v, x2v = a1.view(B_, HW, K1), a2.view(B_, HW, K2)
                 if _side_ok(gvw):
@@ -1086,7 +1107,7 @@ class Linear2Fn(torch.autograd.Function):
                              (x1v, x2v, x32[0], x32[1], pl[0], pl[1]))
                 else:
                     linear_wgrad_x32_raw(x1v, x2v, x32[0], x32[1], pl[0], pl[1], B_, N, out=dw)
-            elif ctx.xs is not None and pl is not None and pl[2] == dy._version and pl[0].numel() == M * N * 4:
+            elif ctx.xs is not None and pl is not None and pl[0].numel() == M * N * 4:
                 if _side_ok(gvw):
                     xs, xsmax = ctx.xs, ctx.xsmax
                     _on_side(lambda: linear_wgrad_planes_raw(xs, xsmax, pl[0], pl[1], M // HW, K1 + K2, N, out=dw),
@@ -1184,12 +1205,11 @@ def _gn_forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset):
     call("mulan_groupnorm_fwd_dyn", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), B,
          HW, groups, float(eps), int(act), float(keep), sv, int(offset), ptr(sd), ptr(ymax), stream())
     if ymax is not None:
-        y._absmax = (ymax, y._version)
+        _leave(y, "_absmax", ymax)
     ctx.save_for_backward(x1, x2, gamma, beta, mean, rstd)
     ctx.meta = (groups, int(act), float(keep), seed, int(offset))
     ctx.gv = (_gv(gamma), _gv(beta))
-    bs = getattr(x1, "_bias_sink", None)       # left by the convolution that produced x1 (see Conv3x3Fn.forward)
-    ctx.bias_sink = bs[:2] if (bs is not None and bs[2] == x1._version and bs[0].numel() == C1) else None
+    ctx.bias_sink = _bias_sink_of(x1, C1)
     return y, x1, x2
 
 
@@ -1205,11 +1225,11 @@ def _gn_backward(ctx, dy, add1=None, add2=None, planes_out=False, add1b=None):
     B, C1 = x1.shape[0], x1.shape[-1]
     C2 = 0 if x2 is None else x2.shape[-1]
     Ct = C1 + C2
-    dymax_in = getattr(dy, "_absmax", None)
+    dymax_in = _left(dy, "_absmax")
     if add1b is not None and add1 is None:
         add1, add1b = add1b, None
     if (planes_out and GN_FUSED_REDUCE and x2 is None and add1 is None and dymax_in is not None and
-            dymax_in[1] == dy._version and C1 % 32 == 0 and C1 // 32 <= 16 and (C1 // groups) % 4 == 0 and
+            C1 % 32 == 0 and C1 // 32 <= 16 and (C1 // groups) % 4 == 0 and
             32 % (C1 // groups) == 0 and B * HW * C1 * 4 < 2 ** 31):
         dxp = torch.empty(B * HW * C1 * 4, device=dy.device, dtype=torch.uint8)
         bound = torch.empty((B, MAX_PARTS), device=dy.device, dtype=torch.int32)
@@ -1220,14 +1240,14 @@ def _gn_backward(ctx, dy, add1=None, add2=None, planes_out=False, add1b=None):
         dgamma = _fresh(gvg) if gvg is not None else torch.empty(C1, device=dy.device, dtype=torch.float32)
         dbeta = _fresh(gvb) if gvb is not None else torch.empty(C1, device=dy.device, dtype=torch.float32)
         sink, sink2 = ctx.bias_sink if ctx.bias_sink is not None else (None, None)
-        call("mulan_groupnorm_bwd_fused_planes", ptr(dy), ptr(dymax_in[0]), ptr(x1), C1, ptr(gamma), ptr(beta), ptr(mean),
+        call("mulan_groupnorm_bwd_fused_planes", ptr(dy), ptr(dymax_in), ptr(x1), C1, ptr(gamma), ptr(beta), ptr(mean),
              ptr(rstd), ptr(dxp), ptr(parts[0]), ptr(parts[1]), B, HW, groups, act, keep, sv, offset, ptr(sd), ptr(bound),
              ptr(csum), ptr(dgamma), ptr(dbeta), ptr(sink), ptr(sink2), ptr(_gn_tickets(dy.device)),
              ptr(getattr(ctx, "keepbits", None)), stream())
         dx1 = _planes_only_grad(x1.shape, dy.device, dxp, bound)
         if sink is not None:
-            dx1._biasdone = (sink, sink2, dx1._version)
-        dx1._colsum = (csum, dx1._version)
+            _leave(dx1, "_biasdone", sink, sink2)
+        _leave(dx1, "_colsum", csum)
         return dx1, None, dgamma, dbeta
     dx1 = torch.empty_like(x1)
     dx2 = torch.empty_like(x2) if x2 is not None else None
@@ -1251,7 +1271,7 @@ def _gn_backward(ctx, dy, add1=None, add2=None, planes_out=False, add1b=None):
              ptr(_c(add1)), ptr(_c(add2)), ptr(_c(add1b)), ptr(csum), ptr(dgamma), ptr(dbeta), ptr(sink), ptr(sink2),
              ptr(_gn_tickets(dy.device)), stream())
         if sink is not None:
-            dx1._biasdone = (sink, sink2, dx1._version)
+            _leave(dx1, "_biasdone", sink, sink2)
     else:
         if add1b is not None:
             add1 = add1 + add1b
@@ -1264,10 +1284,10 @@ def _gn_backward(ctx, dy, add1=None, add2=None, planes_out=False, add1b=None):
             colsum_raw(dgp, 1, B, Ct, out=dgamma.view(1, Ct))
             colsum_raw(dbp, 1, B, Ct, out=dbeta.view(1, Ct))
     if m1 is not None:
-        dx1._absmax = (m1, dx1._version)
+        _leave(dx1, "_absmax", m1)
     if m2 is not None:
-        dx2._absmax = (m2, dx2._version)
-    dx1._colsum = (csum[:, :C1], dx1._version)          # a strided view when there is an x2: consumers take its row stride
+        _leave(dx2, "_absmax", m2)
+    _leave(dx1, "_colsum", csum[:, :C1])                # a strided view when there is an x2: consumers take its row stride
     return dx1, dx2, dgamma, dbeta
 
 
@@ -1284,6 +1304,16 @@ class GroupNormFn(torch.autograd.Function):
         return _gn_backward(ctx, dy) + (None,) * 6
 
 
+def _skip_outputs(ctx, y, x1, x2, tagged=None):
+    """(y, s1) or (y, s1, s2): y with the aliases of x1 (, x2) for the block's skip path.  The maxima a producer left on
+    x (on `tagged`, where x1 / x2 are contiguous copies of what the caller was given) stay valid for the alias."""
+    t1, t2 = (x1, x2) if tagged is None else tagged
+    s1 = _carry(t1, x1.view_as(x1), tags=("_absmax",))
+    s2 = _carry(t2, x2.view_as(x2), tags=("_absmax",)) if x2 is not None else None
+    ctx.has2 = x2 is not None
+    return (y, s1, s2) if ctx.has2 else (y, s1)
+
+
 class GroupNormSkipFn(torch.autograd.Function):
     """(y, s1, s2) with y as GroupNormFn and s1 / s2 aliases of x1 / x2 for the block's skip path (the ResnetBlock
     residual or nin_shortcut, ldm/model_vdm.py:652-656): the gradients that come back through s1 / s2 are added
@@ -1292,14 +1322,7 @@ class GroupNormSkipFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset):
         y, x1c, x2c = _gn_forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset)
-        s1 = x1c.view_as(x1c)
-        s2 = x2c.view_as(x2c) if x2c is not None else None
-        for src, dst in ((x1, s1), (x2, s2)):                 # the maxima a producer left on x stay valid for the alias
-            c = getattr(src, "_absmax", None) if src is not None else None
-            if c is not None and c[1] == src._version:
-                dst._absmax = (c[0], dst._version)
-        ctx.has2 = x2c is not None
-        return (y, s1, s2) if ctx.has2 else (y, s1)
+        return _skip_outputs(ctx, y, x1c, x2c, tagged=(x1, x2))
 
     @staticmethod
     @once_differentiable
@@ -1358,11 +1381,36 @@ def _gn_fwd_stream_on(B):
 
 def _gn_stats_of(x, C):
     """the partial sums the convolution that produced x left on it: [B, row tiles (4, 8 or 16), C / 4, 2], or None"""
-    c = getattr(x, "_gnstats", None) if x is not None else None
-    if (c is not None and c[1] == x._version and c[0].dim() == 4 and c[0].shape[0] == x.shape[0] and
-            c[0].shape[1] in (H // 8, H // 4, H // 2) and tuple(c[0].shape[2:]) == (C // 4, 2)):
-        return c[0]
+    c = _left(x, "_gnstats")
+    if (c is not None and c.dim() == 4 and c.shape[0] == x.shape[0] and
+            c.shape[1] in (H // 8, H // 4, H // 2) and tuple(c.shape[2:]) == (C // 4, 2)):
+        return c
     return None
+
+
+def _gn_stats_pair(x1, x2, C1, C2):
+    """(st1, st2) of [x1 | x2] -- st2 None without an x2 -- or (None, None): the statistics must be there for both inputs
+    and over the same number of row tiles"""
+    st1 = _gn_stats_of(x1, C1)
+    st2 = _gn_stats_of(x2, C2) if (st1 is not None and x2 is not None) else None
+    if st1 is None or (x2 is not None and (st2 is None or st2.shape[1] != st1.shape[1])):
+        return None, None
+    return st1, st2
+
+
+def _conv_outputs(B, N, dev, bias, cbias, res, want_stats):
+    """what a GroupNorm-fed convolution launch writes and reads besides its operands: y, ymax (None where the launch has
+    more blocks per image than maxima slots), the cbias mode, contiguous bias / cbias / res, and -- want_stats -- ystats:
+    one row of partial sums per row tile of that launch (8, 4 or 2 image rows) for the GroupNorm behind it"""
+    y = torch.empty((B, HW, N), device=dev, dtype=torch.float32)
+    ymax = torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32) if (H // 8) * (N // 128) <= MAX_PARTS else None
+    mode = 0 if cbias is None else (1 if cbias.dim() == 2 else 2)
+    bias_c, cb_c, res_c = _c(bias), _c(cbias), _c(res)
+    ystats = None
+    if want_stats:
+        rows = lib.load().mulan_conv3x3_f16x3_tile_rows(B, H, N, int(ymax is not None))
+        ystats = torch.empty((B, H // rows, N // 4, 2), device=dev, dtype=torch.float32)
+    return y, ymax, mode, bias_c, cb_c, res_c, ystats
 
 
 def gn_conv_ok(C1, C2, N, groups):
@@ -1387,8 +1435,7 @@ class GnConv3x3Fn(torch.autograd.Function):
                 x1_grad_planes=False):
         # x1_grad_planes: the caller vouches that x1 has no consumer besides this op (conv1's output inside a
         # ResnetBlock); if x1's producer accepts it (tag below), d x1 then travels as split planes only
-        acc = getattr(x1, "_accepts_grad_planes", None)
-        ctx.x1_grad_planes = bool(x1_grad_planes and not skip and x2 is None and acc is not None and acc == x1._version)
+        ctx.x1_grad_planes = bool(x1_grad_planes and not skip and x2 is None and _left(x1, "_accepts_grad_planes"))
         # x1 is a block output that also feeds a skip connection (tee): this op's GroupNorm backward will add the gradient
         # that arrives through that connection (it is there first: the up path runs first in the backward pass)
         box = getattr(x1, "_grad_box", None)
@@ -1421,10 +1468,7 @@ class GnConv3x3Fn(torch.autograd.Function):
         # dropout: 30.2 vs 27.7 us, the slab kernel stays), see GN_FWD_STREAM
         st1 = st2 = None
         if _gn_fwd_stream_on(B) and (float(keep) < 1.0 or C2 > 0) and Ct // 32 <= MAX_PARTS:
-            st1 = _gn_stats_of(x1, C1)
-            st2 = _gn_stats_of(x2, C2) if (st1 is not None and x2 is not None) else None
-            if st1 is None or (x2 is not None and (st2 is None or st2.shape[1] != st1.shape[1])):
-                st1 = st2 = None
+            st1, st2 = _gn_stats_pair(x1, x2, C1, C2)
         if st1 is not None:
             if want_bits:
                 keepbits = torch.empty(B * (Ct // 32) * 1024, device=dev, dtype=torch.int32)
@@ -1441,21 +1485,14 @@ class GnConv3x3Fn(torch.autograd.Function):
                  B, HW, groups, float(eps), int(act), float(keep), sv, int(offset), ptr(sd), ptr(bound), stream())
         ctx.keepbits = keepbits
         wp, wmax = _pack_weights(w, Ct, N, 0)
-        y = torch.empty((B, HW, N), device=dev, dtype=torch.float32)
-        ymax = torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32) if (H // 8) * (N // 128) <= MAX_PARTS else None
-        mode = 0 if cbias is None else (1 if cbias.dim() == 2 else 2)
-        bias_c, cb_c, res_c = _c(bias), _c(cbias), _c(res)
-        ystats = None
-        if _gn_fwd_stream_on(B) and N // 32 <= MAX_PARTS:   # by-product for the GroupNorm behind this convolution (see above)
-            rows = lib.load().mulan_conv3x3_f16x3_tile_rows(B, H, N, int(ymax is not None))
-            ystats = torch.empty((B, H // rows, N // 4, 2), device=dev, dtype=torch.float32)
+        # ystats: by-product for the GroupNorm behind this convolution (see above)
+        y, ymax, mode, bias_c, cb_c, res_c, ystats = _conv_outputs(B, N, dev, bias, cbias, res,
+                                                                   _gn_fwd_stream_on(B) and N // 32 <= MAX_PARTS)
         _timed("conv3x3_f16x3_kernel<planes_in>", 2.0 * B * HW * 9 * Ct * N,
                lambda: call("mulan_conv3x3_fwd_f16x3_planes_in_stats", ptr(ys), ptr(bound), ptr(wp), ptr(wmax), ptr(bias_c),
                             ptr(cb_c), mode, ptr(res_c), ptr(y), ptr(ymax), ptr(ystats), 1, B, H, W, Ct, N, stream()))
-        if ystats is not None:
-            y._gnstats = (ystats, y._version)
         return GnConv3x3Fn._finish_forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, mean, rstd, ys, bound, wmax, y, ymax,
-                                           (groups, int(act), float(keep), seed, int(offset)), skip, mode)
+                                           ystats, (groups, int(act), float(keep), seed, int(offset)), skip, mode)
 
     @staticmethod
     def _forward_fill(ctx, x1, x2, gamma, beta, w, bias, cbias, res, groups, eps, act, skip, bound, mean, rstd):
@@ -1465,64 +1502,47 @@ class GnConv3x3Fn(torch.autograd.Function):
         C2 = 0 if x2 is None else x2.shape[-1]
         Ct, N, dev = C1 + C2, w.shape[-1], x1.device
         want_planes = bool(ctx.needs_input_grad[4])
-        st1 = _gn_stats_of(x1, C1) if GN_FILL_STATS and not want_planes else None
-        st2 = _gn_stats_of(x2, C2) if (st1 is not None and x2 is not None) else None
-        if st1 is None or (x2 is not None and (st2 is None or st2.shape[1] != st1.shape[1])):
-            st1 = st2 = None
+        st1, st2 = _gn_stats_pair(x1, x2, C1, C2) if GN_FILL_STATS and not want_planes else (None, None)
+        if st1 is None:
             call("mulan_groupnorm_stats", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(bound), B,
                  HW, groups, float(eps), stream())
         ys = torch.empty(B * HW * Ct * 4 if want_planes else 0, device=dev, dtype=torch.uint8)
         ctx.keepbits = None
         wp, wmax = _pack_weights(w, Ct, N, 0)
-        y = torch.empty((B, HW, N), device=dev, dtype=torch.float32)
-        ymax = torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32) if (H // 8) * (N // 128) <= MAX_PARTS else None
-        mode = 0 if cbias is None else (1 if cbias.dim() == 2 else 2)
-        bias_c, cb_c, res_c = _c(bias), _c(cbias), _c(res)
-        ystats = None
-        if GN_FILL_STATS and not want_planes:     # one row of partial sums per row tile of THIS launch (8, 4 or 2 image rows)
-            rows = lib.load().mulan_conv3x3_f16x3_tile_rows(B, H, N, int(ymax is not None))
-            ystats = torch.empty((B, H // rows, N // 4, 2), device=dev, dtype=torch.float32)
+        y, ymax, mode, bias_c, cb_c, res_c, ystats = _conv_outputs(B, N, dev, bias, cbias, res,
+                                                                   GN_FILL_STATS and not want_planes)
         _timed("conv3x3_f16x3_kernel<gn_in>", 2.0 * B * HW * 9 * Ct * N,
                lambda: call("mulan_conv3x3_fwd_f16x3_gn_in", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(mean),
                             ptr(rstd), groups, int(act), float(eps), ptr(bound), ptr(st1), ptr(st2),
                             0 if st1 is None else int(st1.shape[1]), ptr(wp), ptr(wmax),
                             ptr(bias_c), ptr(cb_c), mode, ptr(res_c), ptr(y), ptr(ymax), ptr(ystats),
                             ptr(ys) if want_planes else None, B, H, W, N, stream()))
-        if ystats is not None:
-            y._gnstats = (ystats, y._version)
         return GnConv3x3Fn._finish_forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, mean, rstd, ys, bound, wmax, y, ymax,
-                                           (groups, int(act), 1.0, 0, 0), skip, mode)
+                                           ystats, (groups, int(act), 1.0, 0, 0), skip, mode)
 
     @staticmethod
-    def _finish_forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, mean, rstd, ys, bound, wmax, y, ymax, meta, skip, mode):
+    def _finish_forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, mean, rstd, ys, bound, wmax, y, ymax, ystats, meta,
+                        skip, mode):
         B, C1 = x1.shape[0], x1.shape[-1]
         Ct, N = C1 + (0 if x2 is None else x2.shape[-1]), w.shape[-1]
         if ymax is not None:
-            y._absmax = (ymax, y._version)
+            _leave(y, "_absmax", ymax)
+        if ystats is not None:
+            _leave(y, "_gnstats", ystats)
         ctx.save_for_backward(x1, x2, gamma, beta, mean, rstd, ys, w, bound)
         ctx.meta = meta
         ctx.wmax = wmax
         ctx.has = (bias is not None, None if cbias is None else cbias.dim(), res is not None)
         ctx.gv_gn = (_gv(gamma), _gv(beta))
         ctx.gv_conv = (_gv(w), _gv(bias))
-        bs = getattr(x1, "_bias_sink", None)       # left by the convolution that produced x1
-        ctx.bias_sink = bs[:2] if (bs is not None and bs[2] == x1._version and bs[0].numel() == C1) else None
+        ctx.bias_sink = _bias_sink_of(x1, C1)
         if ctx.gv_conv[1] is not None and ctx.needs_input_grad[5]:
-            twin = getattr(res, "_bias_twin", None) if res is not None else None
-            y._bias_sink = (ctx.gv_conv[1], twin[0] if (twin is not None and twin[1] == res._version) else None, y._version)
+            _leave_bias_sink(y, ctx.gv_conv[1], res)
         ctx.skip = bool(skip)
         ctx.has2 = x2 is not None
         if res is None and mode != 2 and grad_planes_eligible(Ct, N):
-            y._accepts_grad_planes = y._version      # this op's backward understands a planes-only output gradient
-        if not skip:
-            return y
-        s1 = x1.view_as(x1)
-        s2 = x2.view_as(x2) if x2 is not None else None
-        for src, dst in ((x1, s1), (x2, s2)):                 # the maxima a producer left on x stay valid for the alias
-            c = getattr(src, "_absmax", None) if src is not None else None
-            if c is not None and c[1] == src._version:
-                dst._absmax = (c[0], dst._version)
-        return (y, s1, s2) if ctx.has2 else (y, s1)
+            _leave(y, "_accepts_grad_planes")        # this op's backward understands a planes-only output gradient
+        return _skip_outputs(ctx, y, x1, x2) if skip else y
 
     @staticmethod
     @once_differentiable
