@@ -16,6 +16,7 @@ All tensor math runs in libmulan_hip.so (mulan_amd.ops); there is no CPU path.
 """
 import dataclasses
 import functools
+import logging
 import math
 import os
 import numpy as np
@@ -163,6 +164,31 @@ class _Drop:
 SAMPLER_GRAPH = os.environ.get("MULAN_SAMPLER_GRAPH", "1") == "1"
 
 
+def _capture(run):
+    """run() as a HIP graph -> (the graph, what run() returned inside the capture).  Two eager runs come first: every
+    kernel configured, the allocator warm."""
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    # (thread_local: the RCCL watchdog thread of a multi-rank job keeps polling its events during the capture)
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        out = run()
+    return graph, out
+
+
+def _graphed_or_eager(graph, device, graphed, eager, warning):
+    """graphed() where `graph` asks for a replayed HIP graph and `device` is a GPU, else eager(); the replay is an
+    optimisation, so a capture that fails falls back to eager() loudly (`warning`: the log line, with the exception's
+    type and text as its two arguments)"""
+    if graph and torch.device(device).type == "cuda":
+        try:
+            return graphed()
+        except Exception as e:      # noqa: BLE001
+            logging.getLogger("mulan").warning(warning, type(e).__name__, e)
+    return eager()
+
+
 class GraphedReverseStep:
     """One reverse step of the ancestral sampler (VDM.sample / conditional_sample, ldm/model_mulan_velocity.py:281-350)
     captured as a HIP graph and replayed T times.  What changes from step to step reaches the kernels through static
@@ -176,14 +202,10 @@ class GraphedReverseStep:
         f32 = dict(device=device, dtype=torch.float32)
         self.z_in, self.eps = torch.zeros((B, D), **f32), torch.zeros((B, D), **f32)
         self.t, self.s = torch.full((B,), 1.0, **f32), torch.full((B,), 1.0 - 1.0 / T, **f32)
+        ctx = dict(emb=embedding, cond=conditioning, coeffs=coeffs)     # (as conditional_sample hands it over)
         with torch.no_grad():
-            for _ in range(2):         # eager first: every kernel configured, the allocator warm
-                model._reverse_step(params, self.z_in, self.eps, self.t, self.s, embedding, conditioning, coeffs)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            # (thread_local: the RCCL watchdog thread of a multi-rank job keeps polling its events during the capture)
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.z_out = model._reverse_step(params, self.z_in, self.eps, self.t, self.s, embedding, conditioning, coeffs)
+            self.graph, self.z_out = _capture(
+                lambda: model._reverse_step(params, self.z_in, self.eps, self.t, self.s, ctx))
 
     def step(self, i, z, rng):
         B, T = self.B, self.T
@@ -255,12 +277,7 @@ class GraphedFastStep:
         self.g_prev = torch.full(model._fast_gamma_shape(B), float("nan"), **f32)
         run = lambda: model._fast_step(params, self.z_in, self.t, self.s, self.g_prev, self.x_prev, self.ctx)
         with torch.no_grad():
-            for _ in range(2):         # eager first: every kernel configured, the allocator warm
-                run()
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.z_out, self.x_out, self.g_out = run()
+            self.graph, (self.z_out, self.x_out, self.g_out) = _capture(run)
         self.has_history = False
 
     def set_context(self, ctx):
@@ -315,12 +332,7 @@ class GraphedOdeFunction:
         self.div = torch.empty((B,), **f32) if with_div else None
         run = lambda: model.reverse_ode(params, self.x, ctx, None, self.probe, drift_out=self.drift, div_out=self.div,
                                         tt=self.tt, **({"high_precision": True} if high_precision else {}))
-        for _ in range(2):             # eager first: every kernel configured, the allocator warm
-            run()
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            run()
+        self.graph, _ = _capture(run)          # (no no_grad around it: the Hutchinson term differentiates the U-Net)
 
     def set_context(self, ctx):
         self.ctx["emb"].copy_(ctx["emb"])
@@ -343,9 +355,7 @@ def ode_function(model, params, ctx, B, device, with_div, graph=None, cache=None
     replayed HIP graph by default (MULAN_ODE_GRAPH), eager where the capture fails (logged).  cache (a dict the caller
     keeps while the weights stay as they are): the captured graph of a batch size is re-used for the next batch / the
     next importance sample with its context re-targeted (the packed weights live in persistent buffers, ops.ParamPacker)"""
-    if graph is None:
-        graph = ODE_GRAPH
-    if graph and torch.device(device).type == "cuda":
+    def graphed():
         # the key names what the captured kernels were chosen by: batch, with / without the divergence term and the
         # arithmetic mode (as GraphedStep.matches does; the developer tuning words of mulan_set_tuning are not product
         # state: a caller that flips them drops the cache); the parameter tree is held by the entry and compared by identity -- an id() alone could be re-used by a new tree once the old one is freed
@@ -356,20 +366,17 @@ def ode_function(model, params, ctx, B, device, with_div, graph=None, cache=None
         if hit is not None and hit.params is params:
             hit.set_context(ctx)
             return hit
-        try:
-            g = GraphedOdeFunction(model, params, ctx, B, device, with_div, high_precision)
-            g.params = params
-            if cache is not None:
-                cache.clear()            # (one graph at a time: its pool holds a forward + backward pass of activations)
-                cache[key] = g
-            return g
-        except Exception as e:      # noqa: BLE001  the replay is an optimisation: fall back loudly
-            import logging
-            logging.getLogger("mulan").warning("HIP-graph capture of the ODE function evaluation failed (%s: %s); "
-                                               "evaluating eagerly", type(e).__name__, e)
+        g = GraphedOdeFunction(model, params, ctx, B, device, with_div, high_precision)
+        if cache is not None:
+            cache.clear()            # (one graph at a time: its pool holds a forward + backward pass of activations)
+            cache[key] = g
+        return g
+
     hp = {"high_precision": True} if high_precision else {}
-    return lambda t, x, probe, drift_out, div_out=None: model.reverse_ode(params, x, ctx, t, probe, drift_out=drift_out,
-                                                                          div_out=div_out, **hp)
+    eager = lambda t, x, probe, drift_out, div_out=None: model.reverse_ode(params, x, ctx, t, probe,
+                                                                           drift_out=drift_out, div_out=div_out, **hp)
+    return _graphed_or_eager(ODE_GRAPH if graph is None else graph, device, graphed, lambda: eager,
+                             "HIP-graph capture of the ODE function evaluation failed (%s: %s); evaluating eagerly")
 
 
 def drop_ode_graphs(cache):
@@ -503,6 +510,17 @@ def encode_images(images_u8):
 
 # ----------------------------------------------------------------------------- VDM variants
 class _VDMBase:
+    """What runs a trained model -- the ancestral step (_reverse_step), the few-step samplers (_fast_step), the
+    probability-flow ODE (_ode_eval) and decoding (generate_x) -- is written once here, over what a model supplies (ctx:
+    its per-batch context, fast_context / ode_context):
+      _fast_gamma(params, ctx, t) ...... gamma at the times of a [B] device tensor; _fast_gamma_shape(B): its shape
+      _ode_gamma(params, ctx, t) ....... (gamma, d gamma / d t) there
+      _fast_net(params, z, g_t, ctx) ... the network output at z [B, 3072] for that gamma
+      _fast_mode(), _ancestral_mode(), _ode_mode() ... how mulan_fast_sampler_step, mulan_ancestral_step and
+          mulan_ode_drift / mulan_ode_div read that output: three words, since each kernel numbers its own forms
+      _g_0(params, coeffs, B, device) .. gamma at t = 0, for decoding
+      reverse_ode(params, x, ctx, t, hutch, drift_out, div_out) ... forms the inputs of _ode_eval"""
+
     def __init__(self, config: VDMConfig):
         self.config = config
 
@@ -562,10 +580,55 @@ class _VDMBase:
     def __call__(self, params, *a, **kw):
         return self.apply(params, *a, **kw)
 
+    # ---- ancestral sampler and decoding ---------------------------------------------------------------------------
+    def _step_inputs(self, i, T, z_t, rng):
+        """-> reverse step i of T: z_t as [B, 3072], its noise (rng folded with i), t = (T-i)/T, s = (T-i-1)/T as [B]"""
+        B = z_t.shape[0]
+        z = z_t.reshape(B, D).contiguous()
+        eps = rng.fold_in(i).normal((B, D), z.device)
+        t = torch.full((B,), float(np.float32((T - i) / T)), device=z.device, dtype=torch.float32)
+        s = torch.full((B,), float(np.float32((T - i - 1) / T)), device=z.device, dtype=torch.float32)
+        return z, eps, t, s
+
+    def _reverse_step(self, params, z, eps, t, s, ctx):
+        """the device work of one reverse step t -> s: z, eps [B, 3072]; t, s [B] device tensors"""
+        g_t = self._fast_gamma(params, ctx, t)
+        g_s = self._fast_gamma(params, ctx, s)
+        net = self._fast_net(params, z, g_t, ctx)
+        return ops.ancestral_step(z, net, g_t, g_s, eps, self._ancestral_mode())
+
+    def generate_x(self, params, z_0, coeffs=None, rng=None):
+        """argmax of the decoder logits, or with sample_softmax a categorical draw (rng: the 'sample' Key)"""
+        if self.config.sample_softmax and rng is None:
+            raise ValueError("sample_softmax=True needs rng (the reference's make_rng('sample'))")
+        with torch.no_grad():
+            B = z_0.shape[0]
+            g_0 = self._g_0(params, coeffs, B, z_0.device)
+            if self.config.sample_softmax:
+                return ops.decode_sample(z_0.reshape(B, D), g_0, rng.v).view(B, 32, 32, 3)
+            return ops.decode_argmax(z_0.reshape(B, D), g_0).view(B, 32, 32, 3)
+
+    # ---- probability-flow ODE ---------------------------------------------------------------------------------------
+    def _ode_eval(self, params, x, gt, gp, g_in, cond, mode, hutch, drift_out, div_out):
+        """the drift at x [B, 3072] for gamma gt and its time derivative gp (g_in: gamma as the network takes it); with
+        `hutch` also the Hutchinson estimate hutch^T (d drift / d x) hutch per sample through the U-Net's input
+        gradient (notebook_utils._get_value_div_fn): -> (drift, div | None)"""
+        cfg = self.config
+        B = x.shape[0]
+        xin = x.detach().reshape(B, D).contiguous()
+        if hutch is None:
+            with torch.no_grad():
+                net = score_unet(params["score_model"], cfg, xin.view(B, HW, 3), g_in, cond, _Drop(None, 0.0))
+                drift, _ = ops.ode_drift(net.reshape(B, D), xin, gt, gp, None, mode, drift_out)
+            return drift, None
+        xin.requires_grad_(True)
+        with torch.enable_grad():
+            net = score_unet(params["score_model"], cfg, xin.view(B, HW, 3), g_in, cond, _Drop(None, 0.0))
+        drift, cot = ops.ode_drift(net.detach().reshape(B, D), xin.detach(), gt, gp, hutch, mode, drift_out)
+        (gx,) = torch.autograd.grad(net, xin, cot.view_as(net))
+        return drift, ops.ode_div(gx.reshape(B, D), gt, gp, hutch, mode, div_out)
+
     # ---- deterministic few-step samplers (mulan_amd.sampling; not in the reference) --------------------------------
-    # A model supplies _fast_gamma (gamma at the times of a [B] device tensor), _fast_net (the network output at z_t),
-    # _fast_mode (how mulan_fast_sampler_step reads that output) and _fast_gamma_shape.  ctx: the per-batch context
-    # (MuLAN: the embedding and the schedule coefficients; the plain VDM: the conditioning only).
     def _fast_step(self, params, z, t, s, g_prev, x_prev, ctx):
         """the device work of one step t -> s: (z_s, x_hat_t, gamma_t); g_prev / x_prev None: first order"""
         g_t = self._fast_gamma(params, ctx, t)
@@ -578,16 +641,10 @@ class _VDMBase:
         """-> step(z, t, s, order) of the few-step samplers: a replayed HIP graph (GraphedFastStep) by default
         (MULAN_SAMPLER_GRAPH), eager where the capture fails (logged) or graph=False (EagerFastStep); both take the next
         batch's context through set_context()"""
-        if graph is None:
-            graph = SAMPLER_GRAPH
-        if graph and torch.device(device).type == "cuda":
-            try:
-                return GraphedFastStep(self, params, B, device, ctx)
-            except Exception as e:      # noqa: BLE001  the replay is an optimisation: fall back loudly
-                import logging
-                logging.getLogger("mulan").warning("HIP-graph capture of the few-step sampler's step failed (%s: %s); "
-                                                   "sampling eagerly", type(e).__name__, e)
-        return EagerFastStep(self, params, B, device, ctx)
+        return _graphed_or_eager(SAMPLER_GRAPH if graph is None else graph, device,
+                                 lambda: GraphedFastStep(self, params, B, device, ctx),
+                                 lambda: EagerFastStep(self, params, B, device, ctx),
+                                 "HIP-graph capture of the few-step sampler's step failed (%s: %s); sampling eagerly")
 
     def fast_sample(self, params, z, ctx, sampler="dpm2m", steps=None, t_grid=None, graph=None, stepper=None):
         """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m) over `steps` uniform steps or the explicit t_grid;
@@ -715,7 +772,6 @@ class MulanVDM(_VDMBase):
             return out, dict(emb=emb, zt=zt, net=net, gt=gt, gp=gp, t=t, logits=logits if cfg.reparam_type == 'true' else None)
         return out
 
-
     # ---- ancestral sampler (ldm/model_mulan_velocity.py:270-368, ldm/model_mulan_epsilon.py:365-460) ----------
     def deterministic_embedding(self, B, device):
         """_get_deterministic_embedding (ldm/model_mulan_velocity.py:270-279): topk: the first latent_k entries set;
@@ -733,40 +789,17 @@ class MulanVDM(_VDMBase):
         with torch.no_grad():
             return poly_coefficients(params["gamma"], embedding)
 
-    def _gamma_at(self, coeffs, t_value, B, device):
-        cfg = self.config
-        t = torch.full((B,), float(np.float32(t_value)), device=device, dtype=torch.float32)
-        return self._gamma_of(coeffs, t)                                   # [B, 3072]
-
-    def _gamma_of(self, coeffs, t):
-        """gamma at the times of the device tensor t [B] (the sampler's replayed step reads t from a static buffer)"""
-        cfg = self.config
-        _, _, gt, _ = ops.poly_gamma(coeffs[0], coeffs[1], coeffs[2], t, cfg.gamma_min, cfg.gamma_max)
-        return gt
-
-    def _reverse_step(self, params, z, eps, t, s, embedding, conditioning, coeffs):
-        """the device work of one reverse step t -> s: z, eps [B, 3072]; t, s [B] device tensors"""
-        cfg = self.config
-        B = z.shape[0]
-        g_t = self._gamma_of(coeffs, t)
-        g_s = self._gamma_of(coeffs, s)
-        cond = embedding if cfg.z_conditioning else conditioning.reshape(B, 1).to(torch.float32)
-        g_in = g_t.view(B, HW, 3) if cfg.unet_type == 'ldm' else ops.rowmean(g_t)
-        net = score_unet(params["score_model"], cfg, z.view(B, HW, 3), g_in, cond, _Drop(None, 0.0)).reshape(B, D)
-        return ops.ancestral_step(z, net, g_t, g_s, eps, 0 if self.parameterization == "velocity" else 1)
+    def _ancestral_mode(self):
+        return 0 if self.parameterization == "velocity" else 1      # (velocity_from_epsilon does not reach the sampler)
 
     def conditional_sample(self, params, i, T, z_t, embedding, conditioning, rng, coeffs=None):
         """one reverse step t = (T-i)/T -> s = (T-i-1)/T given the latent embedding; z_t [B,32,32,3] (any layout with
         B x 3072 elements); rng: Key, folded with i like the reference"""
         with torch.no_grad():
-            B = z_t.shape[0]
-            z = z_t.reshape(B, D).contiguous()
-            eps = rng.fold_in(i).normal((B, D), z.device)
+            z, eps, t, s = self._step_inputs(i, T, z_t, rng)
             if coeffs is None:
                 coeffs = self.sample_coefficients(params, embedding)
-            t = torch.full((B,), float(np.float32((T - i) / T)), device=z.device, dtype=torch.float32)
-            s = torch.full((B,), float(np.float32((T - i - 1) / T)), device=z.device, dtype=torch.float32)
-            z_s = self._reverse_step(params, z, eps, t, s, embedding, conditioning, coeffs)
+            z_s = self._reverse_step(params, z, eps, t, s, dict(emb=embedding, cond=conditioning, coeffs=coeffs))
         return z_s.view(z_t.shape)
 
     def reverse_stepper(self, params, B, device, embedding, conditioning, coeffs, T, graph=None):
@@ -775,38 +808,22 @@ class MulanVDM(_VDMBase):
         an idle host it buys nothing (9.66 vs 9.67 ms per step at 16 images, 10.9 vs 10.9 at 64, 18.6 vs 18.7 at 128): below
         ~100 images the step is bound by the latency of its ~450 dependent launches (every one a single round of at most
         256 blocks), not by the host; the replay keeps it that way when the host is busy (data loading, other ranks)."""
-        if graph is None:
-            graph = SAMPLER_GRAPH
-        if graph and torch.device(device).type == "cuda":
-            try:
-                return GraphedReverseStep(self, params, B, device, embedding, conditioning, coeffs, T).step
-            except Exception as e:      # noqa: BLE001  the replay is an optimisation: fall back loudly
-                import logging
-                logging.getLogger("mulan").warning("HIP-graph capture of the sampler's reverse step failed (%s: %s); "
-                                                   "sampling eagerly", type(e).__name__, e)
-        return lambda i, z, rng: self.conditional_sample(params, i, T, z, embedding, conditioning, rng, coeffs)
+        graphed = lambda: GraphedReverseStep(self, params, B, device, embedding, conditioning, coeffs, T).step
+        eager = lambda i, z, rng: self.conditional_sample(params, i, T, z, embedding, conditioning, rng, coeffs)
+        return _graphed_or_eager(SAMPLER_GRAPH if graph is None else graph, device, graphed, lambda: eager,
+                                 "HIP-graph capture of the sampler's reverse step failed (%s: %s); sampling eagerly")
 
     def sample(self, params, i, T, z_t, conditioning, rng, coeffs=None):
         emb = self.deterministic_embedding(z_t.shape[0], z_t.device)
         return self.conditional_sample(params, i, T, z_t, emb, conditioning, rng, coeffs)
 
-    def generate_x(self, params, z_0, coeffs=None, rng=None):
-        """argmax of the decoder logits, or with sample_softmax a categorical draw (rng: the 'sample' Key)"""
-        cfg = self.config
-        if cfg.sample_softmax and rng is None:
-            raise ValueError("sample_softmax=True needs rng (the reference's make_rng('sample'))")
-        with torch.no_grad():
-            B = z_0.shape[0]
-            if coeffs is None:
-                coeffs = self.sample_coefficients(params, self.deterministic_embedding(B, z_0.device))
-            g_0 = self._gamma_at(coeffs, 0.0, B, z_0.device)
-            if cfg.sample_softmax:
-                return ops.decode_sample(z_0.reshape(B, D), g_0, rng.v).view(B, 32, 32, 3)
-            return ops.decode_argmax(z_0.reshape(B, D), g_0).view(B, 32, 32, 3)
+    def _g_0(self, params, coeffs, B, device):
+        if coeffs is None:
+            coeffs = self.sample_coefficients(params, self.deterministic_embedding(B, device))
+        return self._fast_gamma(params, dict(coeffs=coeffs), torch.zeros(B, device=device, dtype=torch.float32))
 
-
-    # ---- few-step deterministic samplers (_VDMBase.fast_sample): the same embedding, conditioning and g_in as
-    # _reverse_step; the network output read as velocity_from_epsilon reads it in reverse_ode (mode 1 = eps_hat)
+    # ---- the samplers' context and hooks (_VDMBase): the few-step samplers read the network output as
+    # velocity_from_epsilon reads it in reverse_ode (mode 1 = eps_hat)
     def fast_context(self, params, embedding, conditioning, coeffs=None):
         """the per-batch context of fast_sample: the embedding, the conditioning and the schedule coefficients"""
         B = embedding.shape[0]
@@ -815,8 +832,13 @@ class MulanVDM(_VDMBase):
         return dict(emb=embedding.contiguous(), cond=conditioning.reshape(B, 1).to(torch.float32).contiguous(),
                     coeffs=tuple(coeffs))
 
+    def _ode_gamma(self, params, ctx, t):
+        cfg = self.config
+        _, _, gt, gp = ops.poly_gamma(*ctx["coeffs"], t, cfg.gamma_min, cfg.gamma_max)
+        return gt, gp                                                      # [B, 3072] each
+
     def _fast_gamma(self, params, ctx, t):
-        return self._gamma_of(ctx["coeffs"], t)
+        return self._ode_gamma(params, ctx, t)[0]
 
     def _fast_gamma_shape(self, B):
         return (B, D)
@@ -829,9 +851,14 @@ class MulanVDM(_VDMBase):
     def _fast_net(self, params, z, g_t, ctx):
         cfg = self.config
         B = z.shape[0]
-        cond = ctx["emb"] if cfg.z_conditioning else ctx["cond"]
-        g_in = g_t.view(B, HW, 3) if cfg.unet_type == 'ldm' else ops.rowmean(g_t)
-        return score_unet(params["score_model"], cfg, z.view(B, HW, 3), g_in, cond, _Drop(None, 0.0)).reshape(B, D)
+        # (the cast: the ancestral step hands over the caller's integer conditioning; fast_context's fp32 passes as is)
+        cond = ctx["emb"] if cfg.z_conditioning else ctx["cond"].reshape(B, 1).to(torch.float32)
+        return score_unet(params["score_model"], cfg, z.view(B, HW, 3), self._g_in(g_t), cond,
+                          _Drop(None, 0.0)).reshape(B, D)
+
+    def _g_in(self, g_t):
+        """gamma as the score model takes it: per pixel (ldm U-Net) or its mean per image"""
+        return g_t.view(g_t.shape[0], HW, 3) if self.config.unet_type == 'ldm' else ops.rowmean(g_t)
 
     # ---- probability-flow ODE (ldm/model_mulan_velocity.py:51-53, 393-421; ldm/model_mulan_epsilon.py:459-478) ----
     def apply_encoder(self, params, images_u8):
@@ -872,28 +899,13 @@ class MulanVDM(_VDMBase):
         hutch^T (d drift / d x) hutch per sample (notebook_utils._get_value_div_fn): returns (drift, div | None).
         tt (optional, [B] fp32 device tensor): the time as a stream-ordered parameter (GraphedOdeFunction) instead of t.
         high_precision: the alpha / sigma selects of ldm/model_mulan_velocity.py:410-417, model_mulan_epsilon.py:472-475"""
-        cfg = self.config
-        mode = self._ode_mode(high_precision)
-        B = x.shape[0]
-        a, b, c = ctx["coeffs"]
         if tt is None:
-            tt = torch.full((B,), float(np.float32(t)), device=x.device, dtype=torch.float32)
+            tt = torch.full((x.shape[0],), float(np.float32(t)), device=x.device, dtype=torch.float32)
         with torch.no_grad():
-            _, _, gt, gp = ops.poly_gamma(a, b, c, tt, cfg.gamma_min, cfg.gamma_max)
-            g_in = gt.view(B, HW, 3) if cfg.unet_type == 'ldm' else ops.rowmean(gt)
-        xin = x.detach().reshape(B, D).contiguous()
-        if hutch is None:
-            with torch.no_grad():
-                net = score_unet(params["score_model"], cfg, xin.view(B, HW, 3), g_in, ctx["emb"], _Drop(None, 0.0))
-                drift, _ = ops.ode_drift(net.reshape(B, D), xin, gt, gp, None, mode, drift_out)
-            return drift, None
-        xin.requires_grad_(True)
-        with torch.enable_grad():
-            net = score_unet(params["score_model"], cfg, xin.view(B, HW, 3), g_in, ctx["emb"], _Drop(None, 0.0))
-        drift, cot = ops.ode_drift(net.detach().reshape(B, D), xin.detach(), gt, gp, hutch, mode, drift_out)
-        (gx,) = torch.autograd.grad(net, xin, cot.view_as(net))
-        div = ops.ode_div(gx.reshape(B, D), gt, gp, hutch, mode, div_out)
-        return drift, div
+            gt, gp = self._ode_gamma(params, ctx, tt)
+            g_in = self._g_in(gt)
+        return self._ode_eval(params, x, gt, gp, g_in, ctx["emb"], self._ode_mode(high_precision), hutch, drift_out,
+                              div_out)
 
 
 class PlainVDM(_VDMBase):
@@ -983,97 +995,73 @@ class PlainVDM(_VDMBase):
             return out, dict(zt=zt, net=net, gt=gt, gp=gp, t=t)
         return out
 
+    # ---- ancestral sampler (ldm/model_vdm.py:182-210), few-step samplers, decoding: the hooks of _VDMBase ------------
+    def sample_coefficients(self, params, embedding):
+        """the scalar schedule has no per-batch coefficients"""
+        return None
 
-def _plain_sample(self, params, i, T, z_t, conditioning, rng, coeffs=None):
-    """model_vdm.VDM.sample (ldm/model_vdm.py:182-210)"""
-    cfg = self.config
-    with torch.no_grad():
-        B = z_t.shape[0]
-        z = z_t.reshape(B, D).contiguous()
-        eps = rng.fold_in(i).normal((B, D), z.device)
-        ones = torch.ones(B, device=z.device)
-        g_t, _ = self._gamma(params, float(np.float32((T - i) / T)) * ones)
-        g_s, _ = self._gamma(params, float(np.float32((T - i - 1) / T)) * ones)
-        cond = conditioning.reshape(B, 1).to(torch.float32)
-        net = score_unet(params["score_model"], cfg, z.view(B, HW, 3), g_t.contiguous(), cond, _Drop(None, 0.0))
-        z_s = ops.ancestral_step(z, net.reshape(B, D), g_t.contiguous(), g_s.contiguous(), eps,
-                                 2 if cfg.reparam_type == 'input' else 1)
-    return z_s.view(z_t.shape)
+    def fast_context(self, params, embedding, conditioning, coeffs=None):
+        """the samplers' context of model_vdm.VDM: the conditioning (there is no embedding and no coefficient)"""
+        B = conditioning.shape[0]
+        return dict(cond=conditioning.reshape(B, 1).to(torch.float32).contiguous())
 
-
-def _plain_generate_x(self, params, z_0, coeffs=None, rng=None):
-    if self.config.sample_softmax and rng is None:
-        raise ValueError("sample_softmax=True needs rng (the reference's make_rng('sample'))")
-    with torch.no_grad():
-        B = z_0.shape[0]
-        g_0, _ = self._gamma(params, torch.zeros(B, device=z_0.device))
-        if self.config.sample_softmax:
-            return ops.decode_sample(z_0.reshape(B, D), g_0.contiguous(), rng.v).view(B, 32, 32, 3)
-        return ops.decode_argmax(z_0.reshape(B, D), g_0.contiguous()).view(B, 32, 32, 3)
-
-
-def _plain_apply_encoder(self, params, images_u8):
-    """model_vdm.VDM.apply_encoder (ldm/model_vdm.py:240-241): zeros"""
-    return torch.zeros((images_u8.reshape(-1, D).shape[0], 50), device=images_u8.device, dtype=torch.float32)
-
-
-def _plain_ode_context(self, params, images_u8):
-    logits = self.apply_encoder(params, images_u8)
-    emb, kl = ops.topk_hard(logits, 15)          # all-equal logits: every entry >= the 15th largest -> ones; KL = 0
-    return dict(emb=emb, kl=kl, coeffs=None, logits=logits)
-
-
-def _plain_reverse_ode(self, params, x, ctx, t, hutch=None, drift_out=None, div_out=None):
-    """model_vdm.VDM.reverse_ode (ldm/model_vdm.py:243-260): drift - 0.5 g^2 score with score = -eps_hat / sigma;
-    the score model is conditioned on embeddings[:, :1] like the reference"""
-    cfg = self.config
-    B = x.shape[0]
-    with torch.no_grad():
-        gt, gp = self._gamma(params, torch.full((B,), float(np.float32(t)), device=x.device))
-        gt, gp = gt.contiguous(), gp.contiguous()
-    cond = ctx["emb"][:, :1].contiguous()
-    xin = x.detach().reshape(B, D).contiguous()
-    if hutch is None:
+    def sample(self, params, i, T, z_t, conditioning, rng, coeffs=None):
+        """model_vdm.VDM.sample (ldm/model_vdm.py:182-210)"""
         with torch.no_grad():
-            net = score_unet(params["score_model"], cfg, xin.view(B, HW, 3), gt, cond, _Drop(None, 0.0))
-            drift, _ = ops.ode_drift(net.reshape(B, D), xin, gt, gp, None, 2, drift_out)
-        return drift, None
-    xin.requires_grad_(True)
-    with torch.enable_grad():
-        net = score_unet(params["score_model"], cfg, xin.view(B, HW, 3), gt, cond, _Drop(None, 0.0))
-    drift, cot = ops.ode_drift(net.detach().reshape(B, D), xin.detach(), gt, gp, hutch, 2, drift_out)
-    (gx,) = torch.autograd.grad(net, xin, cot.view_as(net))
-    return drift, ops.ode_div(gx.reshape(B, D), gt, gp, hutch, 2, div_out)
+            z, eps, t, s = self._step_inputs(i, T, z_t, rng)
+            z_s = self._reverse_step(params, z, eps, t, s, self.fast_context(params, None, conditioning))
+        return z_s.view(z_t.shape)
 
+    def _ode_gamma(self, params, ctx, t):
+        gt, gp = self._gamma(params, t)
+        return gt.contiguous(), gp.contiguous()                            # [B] each
 
-def _plain_fast_context(self, params, embedding, conditioning, coeffs=None):
-    """fast_sample's context of model_vdm.VDM: the conditioning (there is no embedding and no coefficient)"""
-    B = conditioning.shape[0]
-    return dict(cond=conditioning.reshape(B, 1).to(torch.float32).contiguous())
+    def _fast_gamma(self, params, ctx, t):
+        return self._gamma(params, t)[0].contiguous()
 
+    def _fast_gamma_shape(self, B):
+        return (B,)
 
-def _plain_fast_gamma(self, params, ctx, t):
-    return self._gamma(params, t)[0].contiguous()
+    def _fast_mode(self):
+        return 2 if self.config.reparam_type == 'input' else 1
 
+    def _ancestral_mode(self):
+        return 2 if self.config.reparam_type == 'input' else 1
 
-def _plain_fast_net(self, params, z, g_t, ctx):
-    """the network of _plain_sample: eps_hat (reparam_type 'noise') or x_hat ('input') at the per-sample gamma"""
-    B = z.shape[0]
-    return score_unet(params["score_model"], self.config, z.view(B, HW, 3), g_t, ctx["cond"], _Drop(None, 0.0)).reshape(B, D)
+    def _ode_mode(self):
+        return 2
 
+    def _fast_net(self, params, z, g_t, ctx):
+        """the network of sample: eps_hat (reparam_type 'noise') or x_hat ('input') at the per-sample gamma"""
+        B = z.shape[0]
+        return score_unet(params["score_model"], self.config, z.view(B, HW, 3), g_t, ctx["cond"],
+                          _Drop(None, 0.0)).reshape(B, D)
 
-PlainVDM.fast_context = _plain_fast_context
-PlainVDM._fast_gamma = _plain_fast_gamma
-PlainVDM._fast_gamma_shape = lambda self, B: (B,)
-PlainVDM._fast_mode = lambda self: 2 if self.config.reparam_type == 'input' else 1
-PlainVDM._fast_net = _plain_fast_net
-PlainVDM.ode_context_from_embedding = lambda self, params, emb: dict(emb=emb, kl=None, coeffs=None, logits=None)
-PlainVDM.apply_encoder = _plain_apply_encoder
-PlainVDM.ode_context = _plain_ode_context
-PlainVDM.reverse_ode = _plain_reverse_ode
-PlainVDM.sample = _plain_sample
-PlainVDM.generate_x = _plain_generate_x
-PlainVDM.sample_coefficients = lambda self, params, embedding: None
+    def _g_0(self, params, coeffs, B, device):
+        return self._fast_gamma(params, None, torch.zeros(B, device=device))
+
+    # ---- probability-flow ODE (ldm/model_vdm.py:240-260) -----------------------------------------------------------
+    def apply_encoder(self, params, images_u8):
+        """model_vdm.VDM.apply_encoder (ldm/model_vdm.py:240-241): zeros"""
+        return torch.zeros((images_u8.reshape(-1, D).shape[0], 50), device=images_u8.device, dtype=torch.float32)
+
+    def ode_context(self, params, images_u8):
+        """the all-ones embedding of the zero logits and its KL term (0); no coefficients"""
+        logits = self.apply_encoder(params, images_u8)
+        emb, kl = ops.topk_hard(logits, 15)          # all-equal logits: every entry >= the 15th largest -> ones; KL = 0
+        return dict(emb=emb, kl=kl, coeffs=None, logits=logits)
+
+    def ode_context_from_embedding(self, params, emb):
+        """the same context for a given embedding"""
+        return dict(emb=emb, kl=None, coeffs=None, logits=None)
+
+    def reverse_ode(self, params, x, ctx, t, hutch=None, drift_out=None, div_out=None):
+        """model_vdm.VDM.reverse_ode (ldm/model_vdm.py:243-260): drift - 0.5 g^2 score with score = -eps_hat / sigma;
+        the score model is conditioned on embeddings[:, :1] like the reference"""
+        with torch.no_grad():
+            gt, gp = self._ode_gamma(params, ctx, torch.full((x.shape[0],), float(np.float32(t)), device=x.device))
+        return self._ode_eval(params, x, gt, gp, gt, ctx["emb"][:, :1].contiguous(), self._ode_mode(), hutch, drift_out,
+                              div_out)
 
 
 # ----------------------------------------------------------------------------- reference-shaped module surface
