@@ -1408,9 +1408,10 @@ MULAN_API int mulan_groupnorm_fwd_stream(const float* x1, const float* x2, int C
   GnArgs a{x1, x2, C1, C2, gamma, beta, y, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev,
            static_cast<unsigned char*>(yplanes), keepbits, 0, xstats1, xstats2, xstats_tiles};
   // tune[20] (dev A/B): quarters of a slab per block -- 0 / 4: 1024 threads, 2: 512, 1: 256 (the maxima array has 16
-  // entries per image: (slabs) x (z blocks) must fit)
+  // entries per image: (slabs) x (z blocks) must fit -- in planes mode too, where every part receives the bound: with
+  // tune[20] = 1 and 256 channels the parts 16 .. 31 of the last image lay behind the end of the array)
   int nsp = g_mulan_tune[20] == 1 ? 1 : (g_mulan_tune[20] == 2 ? 2 : 4);
-  while (ymax && !yplanes && (Ct / 32) * (4 / nsp) > 16) nsp *= 2;
+  while (ymax && (Ct / 32) * (4 / nsp) > 16) nsp *= 2;
   const dim3 grid(B, Ct / 32, 4 / nsp);
   if (nsp == 1) hipLaunchKernelGGL(gn_fwd_stream_kernel<1>, grid, dim3(256), 0, stream, a);
   else if (nsp == 2) hipLaunchKernelGGL(gn_fwd_stream_kernel<2>, grid, dim3(512), 0, stream, a);
