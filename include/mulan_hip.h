@@ -469,6 +469,19 @@ int mulan_decode_logprobs(const float* z, const float* g0, float* out, size_t n,
 int mulan_fast_sampler_step(const float* zt, const float* net, const float* gt, const float* gs, const float* gprev,
                             const float* xprev, float* zs, float* x0, size_t n, int mode, int g_per_sample,
                             mulan_stream_t stream);
+/* One step t -> s of the stochastic few-step samplers (not in the reference): DDIM with eta in [0, 1] and
+ * SDE-DPM-Solver++(2M), per element like mulan_fast_sampler_step and with its x_hat, D, history (gprev / xprev: NULL
+ * pair, NaN sentinel), modes and gamma layouts.  xi holds one standard normal per element (the kernel draws nothing):
+ *   c = -expm1(g_s - g_t),  k_z = (sigma_s / sigma_t) sqrt(1 - eta^2 c),  k_n = eta sigma_s sqrt(c),
+ *   k_x = -alpha_s expm1(-h + log1p(-eta^2 c) / 2),   z_s = k_z z_t + k_x D + k_n xi.
+ * eta = 0 is mulan_fast_sampler_step; eta = 1 at first order is the posterior step of mulan_ancestral_step, at second
+ * order SDE-DPM-Solver++(2M) (midpoint form); second order at 0 < eta < 1 interpolates the two and is no named method.
+ * g_s == g_t returns z_t bit for bit.  The launch is one thread per element (per float4 under the alignment and
+ * divisibility conditions of mulan_fast_sampler_step) over an exact-cover grid.  hipErrorInvalidValue for eta outside
+ * [0, 1] (NaN included), a NULL xi, a grid of more than 2^31 - 1 blocks and what mulan_fast_sampler_step rejects. */
+int mulan_stochastic_sampler_step(const float* zt, const float* net, const float* gt, const float* gs,
+                                  const float* gprev, const float* xprev, const float* xi, float eta, float* zs,
+                                  float* x0, size_t n, int mode, int g_per_sample, mulan_stream_t stream);
 /* out[r] = mean(x[r, :])  (VDM._get_score_model_gt, model_mulan_velocity.py:141-146) */
 int mulan_rowmean(const float* x, float* out, int rows, int cols, mulan_stream_t stream);
 

@@ -1,12 +1,13 @@
 """python -m ldm.sample --config=... --checkpoint_directory=... [--checkpoint N] --n_samples=N --out=FILE.npz
-                      [--sampler dpm2m|ddim|ancestral] [--steps 25] [--batch_size B] [--embedding deterministic|random]
-                      [--seed 0]
+                      [--sampler dpm2m|sde2m|ddim|ancestral] [--eta 0.0] [--steps 25] [--batch_size B]
+                      [--embedding deterministic|random] [--seed 0]
 
 Writes a set of samples of a checkpoint's EMA parameters (Experiment_Colab) to one .npz: `images` (uint8
 [n_samples, 32, 32, 3]) and the run's settings.  Not in the reference, which writes image grids only.  Global batch b
-is drawn from PRNGKey(seed).fold_in(b) alone; under torchrun the batches are dealt round-robin to the ranks and rank 0
-writes the file, so for a fixed --batch_size the file does not depend on the number of ranks.  The flags are checked
-before any device is touched."""
+is drawn from PRNGKey(seed).fold_in(b) alone (the step noise of sde2m and of ddim with --eta > 0 from the third of its
+three sub-keys, folded with the step index: Experiment_Colab.sample_batches); under torchrun the batches are dealt
+round-robin to the ranks and rank 0 writes the file, so for a fixed --batch_size the file does not depend on the number
+of ranks.  The flags are checked before any device is touched."""
 import io
 import json
 import logging
@@ -29,7 +30,8 @@ def make_flags():
     flags.DEFINE_config_file('config', None, 'Training configuration.')
     flags.DEFINE_string('checkpoint_directory', None, 'Work unit directory.')
     flags.DEFINE_string('checkpoint', None, 'Checkpoint to sample from (default: the latest).')
-    flags.DEFINE_string('sampler', 'dpm2m', 'dpm2m / ddim / ancestral')
+    flags.DEFINE_string('sampler', 'dpm2m', 'dpm2m / sde2m / ddim / ancestral')
+    flags.DEFINE_float('eta', 0.0, 'ddim only: 0 deterministic .. 1 the ancestral posterior step, in [0, 1].')
     flags.DEFINE_integer('steps', 25, 'Number of sampling steps (network evaluations per batch).')
     flags.DEFINE_integer('n_samples', None, 'Number of images to write.')
     flags.DEFINE_integer('batch_size', None, 'Images per batch (default: config.training.batch_size_eval).')
@@ -46,6 +48,10 @@ def parse_flags(argv):
     flags = make_flags().parse(argv)
     if flags.sampler not in SAMPLERS:
         raise SystemExit(f"unknown --sampler {flags.sampler!r} (one of {', '.join(SAMPLERS)})")
+    if not 0.0 <= flags.eta <= 1.0:
+        raise SystemExit(f"--eta must lie in [0, 1], got {flags.eta!r}")
+    if flags.eta != 0.0 and flags.sampler != 'ddim':
+        raise SystemExit(f"--eta applies to --sampler=ddim; {flags.sampler!r} takes none")
     if flags.embedding not in EMBEDDINGS:
         raise SystemExit(f"unknown --embedding {flags.embedding!r} (one of {', '.join(EMBEDDINGS)})")
     if flags.steps < 1:
@@ -92,7 +98,7 @@ def main(argv):
     per_rank = math.ceil(n_batches / world)
     root = PRNGKey(flags.seed)
     images = experiment.sample_batches([root.fold_in(b) for b in mine], batch_size, flags.embedding, flags.sampler,
-                                       flags.steps)
+                                       flags.steps, flags.eta)
     local = torch.zeros((per_rank, batch_size, 32, 32, 3), dtype=torch.uint8, device=experiment.device)
     for j, x in enumerate(images):
         local[j].copy_(x)
@@ -100,8 +106,8 @@ def main(argv):
     if rank == 0:
         ordered = np.stack([gathered[b % world, b // world] for b in range(n_batches)])
         out = ordered.reshape(-1, 32, 32, 3)[:flags.n_samples]
-        settings = dict(sampler=flags.sampler, steps=flags.steps, n_samples=flags.n_samples, batch_size=batch_size,
-                        embedding=flags.embedding, seed=flags.seed, checkpoint=str(ckpt_num),
+        settings = dict(sampler=flags.sampler, eta=float(flags.eta), steps=flags.steps, n_samples=flags.n_samples,
+                        batch_size=batch_size, embedding=flags.embedding, seed=flags.seed, checkpoint=str(ckpt_num),
                         vdm_type=flags.config.get('vdm_type', 'vdm'))
         write_npz(flags.out, dict(images=out, settings=np.array(json.dumps(settings, sort_keys=True))))
         print(f'wrote {out.shape[0]} samples ({flags.sampler}, {flags.steps} steps) to {flags.out}')

@@ -247,3 +247,119 @@ MULAN_API int mulan_fast_sampler_step(const float* zt, const float* net, const f
                        xprev, zs, x0, n, mode, g_per_sample);
   MULAN_CHECK_LAUNCH();
 }
+
+// ---- stochastic few-step samplers: DDIM with eta in [0, 1] and SDE-DPM-Solver++(2M) per element ---------------------
+// The step above with fresh noise xi ~ N(0, 1) per element, read from a buffer (the kernel draws nothing).  With
+// h = (g_t - g_s) / 2, c = -expm1(g_s - g_t) = 1 - e^(-2h), x_hat and D as in fast_step_elem:
+//   k_z = (sigma_s / sigma_t) sqrt(1 - eta^2 c)
+//   k_x = -alpha_s expm1(u),  u = -h + log1p(-eta^2 c) / 2     (= alpha_s (1 - e^(-h) sqrt(1 - eta^2 c)))
+//   k_n = eta sigma_s sqrt(c)
+//   z_s = k_z z_t + k_x D + k_n xi
+// Known answers (tests/test_gpu_stochastic_sampler.py holds the kernel to each):
+//   eta = 0: k_z = sigma_s / sigma_t, k_x = -alpha_s expm1(-h), k_n = 0: mulan_fast_sampler_step, i.e. DDIM at first
+//     order and DPM-Solver++(2M) at second.
+//   eta = 1, first order: k_z = (sigma_s / sigma_t) e^(-h), k_x = alpha_s c, k_n = sigma_s sqrt(c) = sqrt(sigmoid(g_s) c):
+//     the ancestral posterior step of ancestral_step_kernel, which is also the first-order SDE-DPM-Solver++ step.
+//   eta = 1, second order: SDE-DPM-Solver++(2M) in its midpoint form,
+//     z_s = (sigma_s / sigma_t) e^(-h) z_t + alpha_s (1 - e^(-2h)) D + sigma_s sqrt(1 - e^(-2h)) xi.
+//   g_s == g_t: c = 0, so k_z = 1, k_x = 0, k_n = 0 and z_s == z_t bit for bit, for every eta, both orders, any finite xi.
+// Second order with 0 < eta < 1 interpolates the two coefficient sets; it is no named method.
+// 1 - eta^2 c is formed as (1 - eta^2) + eta^2 e^(g_s - g_t): two non-negative terms, so a long step (c -> 1) loses
+// nothing to cancellation, and at g_s == g_t the sum rounds to exactly 1 (the error of 1 - eta^2 is below half an ulp
+// of 1), so k_z is sqrt(x / x) * sqrt(1) = 1 and not a product that rounds away from it.
+namespace {
+
+__device__ __forceinline__ float stochastic_step_elem(float z, float nt, float g_t, float g_s, float g_p, float x_p,
+                                                      float xi, float eta, int mode, bool second, float* xh_out) {
+  const float st2 = sigmoid_f(g_t), ss2 = sigmoid_f(g_s);
+  const float alpha_t = sqrtf(sigmoid_f(-g_t)), sigma_t = sqrtf(st2), alpha_s = sqrtf(sigmoid_f(-g_s));
+  float xh = nt;
+  if (mode == 0) xh = alpha_t * z - sigma_t * nt;
+  if (mode == 1) xh = (z - sigma_t * nt) / alpha_t;
+  *xh_out = xh;
+  const float h = 0.5f * (g_t - g_s);
+  float d = xh;
+  if (second) {
+    const float hp = 0.5f * (g_p - g_t);
+    if (hp > 0.f && hp < INFINITY) {
+      const float w = h / (2.f * hp);
+      d = (1.f + w) * xh - w * x_p;
+    }
+  }
+  const float e2 = eta * eta;
+  const float c = -expm1f(g_s - g_t), q = e2 * c;
+  const float om = fmaf(e2, expf(g_s - g_t), 1.f - e2);          // 1 - eta^2 c
+  const float u = -h + 0.5f * (q < 0.5f ? log1pf(-q) : logf(om));
+  const float k_z = sqrtf(ss2 / st2) * sqrtf(om);
+  const float k_x = -alpha_s * expm1f(u);
+  const float k_n = eta * sqrtf(ss2) * sqrtf(c);
+  return k_z * z + k_x * d + k_n * xi;
+}
+
+// one thread per float4 (VEC) or per element, the grid covers n exactly: no grid-stride loop, no cap
+template <bool VEC>
+__global__ __launch_bounds__(256) void stochastic_sampler_step_kernel(
+    const float* __restrict__ zt, const float* __restrict__ net, const float* __restrict__ gt,
+    const float* __restrict__ gs, const float* __restrict__ gprev, const float* __restrict__ xprev,
+    const float* __restrict__ xi, float eta, float* __restrict__ zs, float* __restrict__ x0, size_t n, int mode,
+    int g_per_sample) {
+  const bool second = gprev != nullptr;
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (VEC) {
+    // n % 4 == 0, every pointer 16-byte aligned, g_per_sample % 4 == 0 (as fast_sampler_step_kernel)
+    if (q >= n / 4) return;
+    const size_t i = q * 4;
+    const float4 z4 = reinterpret_cast<const float4*>(zt)[q], n4 = reinterpret_cast<const float4*>(net)[q];
+    const float4 e4 = reinterpret_cast<const float4*>(xi)[q];
+    float4 gt4, gs4, gp4 = make_float4(0.f, 0.f, 0.f, 0.f), xp4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g_per_sample) {
+      const size_t gi = i / (size_t)g_per_sample;
+      gt4 = make_float4(gt[gi], gt[gi], gt[gi], gt[gi]);
+      gs4 = make_float4(gs[gi], gs[gi], gs[gi], gs[gi]);
+      if (second) gp4 = make_float4(gprev[gi], gprev[gi], gprev[gi], gprev[gi]);
+    } else {
+      gt4 = reinterpret_cast<const float4*>(gt)[q];
+      gs4 = reinterpret_cast<const float4*>(gs)[q];
+      if (second) gp4 = reinterpret_cast<const float4*>(gprev)[q];
+    }
+    if (second) xp4 = reinterpret_cast<const float4*>(xprev)[q];
+    float4 o, x;
+    o.x = stochastic_step_elem(z4.x, n4.x, gt4.x, gs4.x, gp4.x, xp4.x, e4.x, eta, mode, second, &x.x);
+    o.y = stochastic_step_elem(z4.y, n4.y, gt4.y, gs4.y, gp4.y, xp4.y, e4.y, eta, mode, second, &x.y);
+    o.z = stochastic_step_elem(z4.z, n4.z, gt4.z, gs4.z, gp4.z, xp4.z, e4.z, eta, mode, second, &x.z);
+    o.w = stochastic_step_elem(z4.w, n4.w, gt4.w, gs4.w, gp4.w, xp4.w, e4.w, eta, mode, second, &x.w);
+    reinterpret_cast<float4*>(zs)[q] = o;
+    if (x0) reinterpret_cast<float4*>(x0)[q] = x;
+  } else {
+    if (q >= n) return;
+    const size_t gi = g_per_sample ? q / (size_t)g_per_sample : q;
+    float x;
+    zs[q] = stochastic_step_elem(zt[q], net[q], gt[gi], gs[gi], second ? gprev[gi] : 0.f, second ? xprev[q] : 0.f, xi[q],
+                                 eta, mode, second, &x);
+    if (x0) x0[q] = x;
+  }
+}
+
+}  // namespace
+
+MULAN_API int mulan_stochastic_sampler_step(const float* zt, const float* net, const float* gt, const float* gs,
+                                            const float* gprev, const float* xprev, const float* xi, float eta,
+                                            float* zs, float* x0, size_t n, int mode, int g_per_sample,
+                                            hipStream_t stream) {
+  if (n == 0 || mode < 0 || mode > 2 || g_per_sample < 0 || !zt || !net || !gt || !gs || !zs || !xi ||
+      (gprev == nullptr) != (xprev == nullptr) || (g_per_sample && n % (size_t)g_per_sample) || !(eta >= 0.f && eta <= 1.f))
+    return (int)hipErrorInvalidValue;
+  const bool vec = n % 4 == 0 && (g_per_sample % 4) == 0 && aligned16(zt) && aligned16(net) && aligned16(zs) &&
+                   aligned16(x0) && aligned16(xprev) && aligned16(xi) &&
+                   (g_per_sample || (aligned16(gt) && aligned16(gs) && aligned16(gprev)));
+  // every thread owns one float4 (or one element): the grid is the exact cover, refused where it does not fit a launch
+  const size_t nb = ((vec ? n / 4 : n) + 255) / 256;
+  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
+  if (vec)
+    hipLaunchKernelGGL(stochastic_sampler_step_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, zt, net, gt, gs,
+                       gprev, xprev, xi, eta, zs, x0, n, mode, g_per_sample);
+  else
+    hipLaunchKernelGGL(stochastic_sampler_step_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, zt, net, gt, gs,
+                       gprev, xprev, xi, eta, zs, x0, n, mode, g_per_sample);
+  MULAN_CHECK_LAUNCH();
+}

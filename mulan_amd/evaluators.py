@@ -37,48 +37,53 @@ class Experiment_Colab(Experiment_VDM):
         self.rngs = {'sample': sample_rng}
 
     # ---- samplers of the notebook front end (ldm/notebook_utils.py:54-135) --------------------------------------
-    def _embedding_samples(self, embedding, rng, T, sampler='ancestral'):
+    def _embedding_samples(self, embedding, rng, T, sampler='ancestral', eta=0.0):
         """T steps of `sampler` under a fixed [B, 50] embedding (ancestral: model.conditional_sample), then generate_x
         (Experiment_VDM.draw_samples; z_1 ~ N(0, I) as the notebook draws it)"""
         rng = rng.fold_in(self.rank)
         rng, sample_rng = rng.split()
         samples, _ = self.draw_samples(self.params, embedding.shape[0], embedding, sample_rng, rng, rng.fold_in(T),
-                                       sampling.check_sampler(sampler), T)
+                                       sampling.check_sampler(sampler), T, eta=eta)
         return parallel.all_gather_tensor(samples)
 
     @staticmethod
     def _steps(T, sampler):
-        """T of the notebook samplers: 1000 ancestral steps by default, 25 for ddim / dpm2m (as p_sample)"""
+        """T of the notebook samplers: 1000 ancestral steps by default, 25 for ddim / dpm2m / sde2m (as p_sample)"""
         if T is not None:
             return T
         return 1000 if sampling.check_sampler(sampler) == 'ancestral' else 25
 
-    def sample_conditionally(self, embedding, T=None, sampler='ancestral'):
-        """Experiment_Colab.sample_conditionally: an image grid sampled under one 50-dim k-hot embedding (sampler: see
-        Experiment_VDM.sample_fn; T is the step count, by default 1000 ancestral / 25 few-step)"""
+    def sample_conditionally(self, embedding, T=None, sampler='ancestral', eta=0.0):
+        """Experiment_Colab.sample_conditionally: an image grid sampled under one 50-dim k-hot embedding (sampler, eta:
+        see Experiment_VDM.sample_fn; T is the step count, by default 1000 ancestral / 25 few-step)"""
+        sampling.check_eta(sampler, eta)
         B = self.eval_iter.local
         emb = torch.as_tensor(embedding, dtype=torch.float32, device=self.device).reshape(1, -1)
         assert emb.shape[1] == 50
-        samples = self._embedding_samples(emb.expand(B, 50).contiguous(), self.rng, self._steps(T, sampler), sampler)
+        samples = self._embedding_samples(emb.expand(B, 50).contiguous(), self.rng, self._steps(T, sampler), sampler,
+                                          eta)
         return ckpt_lib.generate_image_grids(samples).astype(np.uint8)
 
-    def sample_randomly(self, T=None, sampler='ancestral'):
+    def sample_randomly(self, T=None, sampler='ancestral', eta=0.0):
         """Experiment_Colab.sample_randomly: every image under the hard top-15 embedding of its own random logits"""
         from . import ops
+        sampling.check_eta(sampler, eta)
         B = self.eval_iter.local
         _, embeddings_rng = self.rng.fold_in(self.rank).split()
         emb, _ = ops.topk_hard(embeddings_rng.normal((B, 50), self.device), 15)
-        samples = self._embedding_samples(emb, self.rng, self._steps(T, sampler), sampler)
+        samples = self._embedding_samples(emb, self.rng, self._steps(T, sampler), sampler, eta)
         return ckpt_lib.generate_image_grids(samples).astype(np.uint8)
 
-    def sample_batches(self, keys, batch_size, embedding='deterministic', sampler='dpm2m', steps=25):
+    def sample_batches(self, keys, batch_size, embedding='deterministic', sampler='dpm2m', steps=25, eta=0.0):
         """uint8 [batch_size, 32, 32, 3] per key, each batch drawn from its key alone (the python -m ldm.sample CLI):
-        key.split(3) -> (prior z_1 ~ sigma_prior N(0, I), random embedding logits, per-step noise of the ancestral
-        sampler); generate_x with key.fold_in(steps).  embedding 'deterministic': model.deterministic_embedding (as
-        sample_fn); 'random': the hard top-15 of random normal logits (as sample_randomly).  The few-step samplers re-use
-        one stepper, re-targeted at every batch's context."""
+        key.split(3) -> (prior z_1 ~ sigma_prior N(0, I), random embedding logits, per-step noise); generate_x with
+        key.fold_in(steps).  The per-step noise of the ancestral sampler, of sde2m and of ddim with eta > 0 comes from
+        the third sub-key alone, folded with the step index, so neither z_1 nor the embedding shares a draw with it.
+        embedding 'deterministic': model.deterministic_embedding (as sample_fn); 'random': the hard top-15 of random
+        normal logits (as sample_randomly).  The few-step samplers re-use one stepper, re-targeted at every batch's
+        context."""
         from . import ops
-        sampling.check_sampler(sampler)
+        sampling.check_eta(sampler, eta)
         if embedding not in ('deterministic', 'random'):
             raise ValueError(f"embedding must be 'deterministic' or 'random', got {embedding!r}")
         mulan = hasattr(self.model, "deterministic_embedding")
@@ -91,7 +96,7 @@ class Experiment_Colab(Experiment_VDM):
             if embedding == 'random':
                 emb, _ = ops.topk_hard(k_e.normal((batch_size, 50), self.device), 15)
             x, stepper = self.draw_samples(self.params, batch_size, emb, k_z, k_s, key.fold_in(steps), sampler, steps,
-                                           prior_scale=float(self.config.model.sigma_prior), stepper=stepper)
+                                           prior_scale=float(self.config.model.sigma_prior), stepper=stepper, eta=eta)
             out.append(x)
         return out
 

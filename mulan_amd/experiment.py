@@ -485,7 +485,8 @@ class Experiment(abc.ABC):
         """self.p_sample of the reference (ldm/experiment.py:96-102): sample_fn on a batch shaped like one eval
         micro-batch, samples of all ranks concatenated.  T: config.training.sample_timesteps, default 1000 like the
         reference's hard-coded value; 0 disables sampling at evaluation points.  config.training.sampler (optional, not in
-        the reference): 'ancestral' (the default), 'ddim' or 'dpm2m', which then run sample_timesteps steps (default 25)."""
+        the reference): 'ancestral' (the default), 'ddim', 'dpm2m' or 'sde2m', which then run sample_timesteps steps
+        (default 25)."""
         sampler = sampling.check_sampler(self.config.training.get('sampler', 'ancestral'))
         if T is None:
             T = int(self.config.training.get('sample_timesteps', 1000 if sampler == 'ancestral' else 25))
@@ -565,23 +566,25 @@ class Experiment_VDM(Experiment):
         metrics = {'scalars': scalar_dict, 'images': {'inputs': inputs['images']}}
         return bpd, metrics
 
-    def sample_fn(self, *, dummy_inputs, rng, params, T=1000, gather=True, sampler='ancestral', t_grid=None):
+    def sample_fn(self, *, dummy_inputs, rng, params, T=1000, gather=True, sampler='ancestral', t_grid=None, eta=0.0):
         """Experiment_VDM.sample_fn (ldm/experiment_vdm.py:80-110): z_T ~ sigma_prior N(0, I), T ancestral steps
         (`model.sample`), `model.generate_x`; returns uint8 samples [B (* world), 32, 32, 3].  The noise stream is this
         build's Philox, folded with the rank like the reference folds axis_index.
         sampler (not in the reference): 'ancestral' (the reference's loop), or the deterministic few-step samplers 'ddim' /
         'dpm2m' (mulan_amd.sampling) over T uniform steps or the explicit t_grid (1 -> 0, strictly decreasing: it sets
-        the step count); generate_x then draws with rng.fold_in(N) like the ancestral loop with fold_in(T)."""
-        sampling.check_sampler(sampler)
+        the step count); generate_x then draws with rng.fold_in(N) like the ancestral loop with fold_in(T).
+        'sde2m' (SDE-DPM-Solver++(2M)) and 'ddim' with eta in (0, 1] are the stochastic few-step samplers: step k draws
+        its noise under the key the ancestral loop folds with its step index (rng.fold_in(k) after the split below)."""
+        sampling.check_eta(sampler, eta)
         if sampler == 'ancestral' and t_grid is not None:
-            raise ValueError("t_grid applies to the ddim / dpm2m samplers; the ancestral sampler runs T uniform steps")
+            raise ValueError("t_grid applies to the few-step samplers; the ancestral sampler runs T uniform steps")
         grid = None if sampler == 'ancestral' else sampling.time_grid(None if t_grid is not None else T, t_grid)
         N = T if grid is None else len(grid) - 1
         rng = rng.fold_in(self.rank)
         B = dummy_inputs.shape[0]
         rng, sample_rng = rng.split()
         samples, _ = self.draw_samples(params, B, None, sample_rng, rng, rng.fold_in(N), sampler, N, t_grid=grid,
-                                       prior_scale=float(self.config.model.sigma_prior))
+                                       prior_scale=float(self.config.model.sigma_prior), eta=eta)
         return parallel.all_gather_tensor(samples) if gather else samples
 
     def _packer_for(self, params):
@@ -592,14 +595,16 @@ class Experiment_VDM(Experiment):
         return None
 
     def draw_samples(self, params, B, embedding, prior_rng, step_rng, decode_rng, sampler, steps, t_grid=None,
-                     prior_scale=1.0, stepper=None):
+                     prior_scale=1.0, stepper=None, eta=0.0):
         """One batch of B images, the loop every sampling entry point runs: z_1 = prior_scale * N(0, I) from prior_rng,
         `steps` steps of `sampler` under `embedding` (MuLAN models; None: model.deterministic_embedding) with the per-step
         noise of the ancestral sampler from step_rng (rng.fold_in(i) at step i), generate_x with decode_rng (needed by
         sample_softmax).  The weights are packed once for the whole loop.  ancestral: the reverse step is a replayed HIP
-        graph (model.GraphedReverseStep); ddim / dpm2m (t_grid, if given, sets the step count): model.fast_sample, the
-        stepper re-used when one is given (re-targeted at this batch's context) and returned for the next batch.
+        graph (model.GraphedReverseStep); ddim / dpm2m / sde2m (t_grid, if given, sets the step count):
+        model.fast_sample, the stepper re-used when one is given (re-targeted at this batch's context) and returned for
+        the next batch; sde2m and ddim with eta > 0 draw the noise of step k under step_rng.fold_in(k) as well.
         -> (uint8 [B, 32, 32, 3], stepper or None)"""
+        step_eta = sampling.check_eta(sampler, eta)          # what the steps run with: 1 for sde2m
         packer = self._packer_for(params)
         conditioning = torch.zeros(B, dtype=torch.uint8, device=self.device)
         mulan = hasattr(self.model, "reverse_stepper")
@@ -625,9 +630,9 @@ class Experiment_VDM(Experiment):
                 else:
                     ctx = self.model.fast_context(params, embedding if mulan else None, conditioning)
                     if stepper is None:
-                        stepper = self.model.fast_stepper(params, B, self.device, ctx)
+                        stepper = self.model.fast_stepper(params, B, self.device, ctx, step_eta=step_eta)
                     z = self.model.fast_sample(params, z, ctx, sampler, None if t_grid is not None else steps, t_grid,
-                                               stepper=stepper)
+                                               stepper=stepper, eta=eta, noise=step_rng if step_eta > 0.0 else None)
                     coeffs = ctx.get("coeffs")
                 samples = self.model.generate_x(params, z, coeffs, rng=decode_rng)
             finally:

@@ -115,6 +115,7 @@ SIGNATURES = {
     "mulan_decode_sample": [P, P, P, Z, I, U, U, P],
     "mulan_decode_logprobs": [P, P, P, Z, I, P],
     "mulan_fast_sampler_step": [P, P, P, P, P, P, P, P, Z, I, I, P],
+    "mulan_stochastic_sampler_step": [P, P, P, P, P, P, P, F, P, P, Z, I, I, P],
     "mulan_rowmean": [P, P, I, I, P],
     "mulan_ode_drift": [P, P, P, P, P, P, P, Z, I, I, P],
     "mulan_ode_div": [P, P, P, P, P, I, I, I, I, P],

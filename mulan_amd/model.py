@@ -233,18 +233,35 @@ def _check_fast_context(like, ctx):
                                  f"stepper was built for {None if x is None else tuple(x.shape)}")
 
 
+def _fill_step_noise(buf, noise, k):
+    """the noise of step k of a stochastic few-step sampler into buf [B, 3072]: `noise` is the batch's step key (the
+    draw is ops.randn under key.fold_in(k), as the ancestral steppers draw theirs) or a callable k -> xi"""
+    if noise is None:
+        raise RuntimeError("a stochastic step needs the batch's noise (set_noise: a Key, or a callable k -> xi)")
+    if k is None:
+        raise ValueError("a stochastic step needs its index k (the noise is drawn per step)")
+    if callable(noise):
+        buf.copy_(noise(k).reshape(buf.shape))
+    else:
+        ops.randn(None, noise.fold_in(k).v, 0, buf.device, out=buf)
+    return buf
+
+
 class EagerFastStep:
     """The eager form of GraphedFastStep (MULAN_SAMPLER_GRAPH=0, or a failed capture): sampling.EagerStepper over the
     model's network and schedule, reading the context through this object so that set_context() re-targets it at the
-    next batch like the replayed stepper."""
+    next batch like the replayed stepper.  step_eta > 0 (sampling.check_eta): the stochastic step on the noise
+    set_noise() names."""
 
-    def __init__(self, model, params, B, device, ctx):
+    def __init__(self, model, params, B, device, ctx, step_eta=0.0):
         from . import sampling
-        self.ctx = ctx
+        self.ctx, self.step_eta, self.noise = ctx, float(step_eta), None
         times = lambda t: torch.full((B,), float(np.float32(t)), device=device, dtype=torch.float32)
         gamma_fn = lambda t: model._fast_gamma(params, self.ctx, times(t))
         net_fn = lambda z, t: model._fast_net(params, z.reshape(B, D), gamma_fn(t), self.ctx).view(z.shape)
-        self._make = lambda: sampling.EagerStepper(net_fn, gamma_fn, model._fast_mode())
+        self.xi = torch.zeros((B, D), device=device, dtype=torch.float32) if self.step_eta > 0.0 else None
+        noise_fn = (lambda k: _fill_step_noise(self.xi, self.noise, k)) if self.step_eta > 0.0 else None
+        self._make = lambda: sampling.EagerStepper(net_fn, gamma_fn, model._fast_mode(), self.step_eta, noise_fn)
         self._step = self._make()
 
     def set_context(self, ctx):
@@ -252,8 +269,11 @@ class EagerFastStep:
         self.ctx = ctx
         self._step = self._make()             # no history and no cached gamma of the previous batch
 
-    def __call__(self, z, t, s, order):
-        return self._step(z, t, s, order)
+    def set_noise(self, noise):
+        self.noise = noise
+
+    def __call__(self, z, t, s, order, k=None):
+        return self._step(z, t, s, order, k)
 
 
 class GraphedFastStep:
@@ -265,17 +285,23 @@ class GraphedFastStep:
     embedding and the schedule coefficients of the MuLAN models) sits in buffers of its own: set_context() re-targets the
     graph at the next batch.  The replayed step is bit-identical to the eager one
     (tests/test_gpu_fast_sampler.py::test_replayed_fast_step_equals_the_eager_step).  The weights must stay as they are
-    while the stepper lives (the caller holds the ParamPacker refresh)."""
+    while the stepper lives (the caller holds the ParamPacker refresh).
+    step_eta > 0 captures the stochastic step (DDIM with eta, SDE-DPM-Solver++(2M)) instead: its noise xi is one more static
+    buffer, filled before each replay by the Philox call of the eager stepper (_fill_step_noise, the pattern of
+    GraphedReverseStep.step); step_eta is an argument of the captured launch, so a stepper serves the one it was built
+    for."""
 
-    def __init__(self, model, params, B, device, ctx):
-        self.B = B
+    def __init__(self, model, params, B, device, ctx, step_eta=0.0):
+        self.B, self.step_eta, self.noise = B, float(step_eta), None
         f32 = dict(device=device, dtype=torch.float32)
         self.ctx = {k: (None if v is None else tuple(c.detach().clone() for c in v) if isinstance(v, tuple)
                         else v.detach().clone()) for k, v in ctx.items()}
         self.z_in, self.x_prev = torch.zeros((B, D), **f32), torch.zeros((B, D), **f32)
         self.t, self.s = torch.full((B,), 1.0, **f32), torch.full((B,), 0.5, **f32)
         self.g_prev = torch.full(model._fast_gamma_shape(B), float("nan"), **f32)
-        run = lambda: model._fast_step(params, self.z_in, self.t, self.s, self.g_prev, self.x_prev, self.ctx)
+        self.xi = torch.zeros((B, D), **f32) if self.step_eta > 0.0 else None
+        run = lambda: model._fast_step(params, self.z_in, self.t, self.s, self.g_prev, self.x_prev, self.ctx, self.xi,
+                                       self.step_eta)
         with torch.no_grad():
             self.graph, (self.z_out, self.x_out, self.g_out) = _capture(run)
         self.has_history = False
@@ -290,9 +316,14 @@ class GraphedFastStep:
                 self.ctx[k].copy_(v)
         self.has_history = False
 
-    def __call__(self, z, t, s, order):
+    def set_noise(self, noise):
+        self.noise = noise
+
+    def __call__(self, z, t, s, order, k=None):
         if order == 2 and not self.has_history:
             raise RuntimeError("a second-order step needs the history of a previous step")
+        if self.xi is not None:
+            _fill_step_noise(self.xi, self.noise, k)
         self.z_in.copy_(z.reshape(self.B, D))
         self.t.fill_(float(np.float32(t)))
         self.s.fill_(float(np.float32(s)))
@@ -628,39 +659,57 @@ class _VDMBase:
         (gx,) = torch.autograd.grad(net, xin, cot.view_as(net))
         return drift, ops.ode_div(gx.reshape(B, D), gt, gp, hutch, mode, div_out)
 
-    # ---- deterministic few-step samplers (mulan_amd.sampling; not in the reference) --------------------------------
-    def _fast_step(self, params, z, t, s, g_prev, x_prev, ctx):
-        """the device work of one step t -> s: (z_s, x_hat_t, gamma_t); g_prev / x_prev None: first order"""
+    # ---- few-step samplers (mulan_amd.sampling; not in the reference) ----------------------------------------------
+    def _fast_step(self, params, z, t, s, g_prev, x_prev, ctx, xi=None, step_eta=0.0):
+        """the device work of one step t -> s: (z_s, x_hat_t, gamma_t); g_prev / x_prev None: first order; xi [B, 3072]
+        with step_eta > 0: the stochastic step on that noise"""
         g_t = self._fast_gamma(params, ctx, t)
         g_s = self._fast_gamma(params, ctx, s)
         net = self._fast_net(params, z, g_t, ctx)
-        z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, self._fast_mode(), g_prev, x_prev)
+        if xi is not None:
+            z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, self._fast_mode(), xi, step_eta, g_prev,
+                                                      x_prev)
+        else:
+            z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, self._fast_mode(), g_prev, x_prev)
         return z_s, x0, g_t
 
-    def fast_stepper(self, params, B, device, ctx, graph=None):
-        """-> step(z, t, s, order) of the few-step samplers: a replayed HIP graph (GraphedFastStep) by default
+    def fast_stepper(self, params, B, device, ctx, graph=None, step_eta=0.0):
+        """-> step(z, t, s, order[, k]) of the few-step samplers: a replayed HIP graph (GraphedFastStep) by default
         (MULAN_SAMPLER_GRAPH), eager where the capture fails (logged) or graph=False (EagerFastStep); both take the next
-        batch's context through set_context()"""
+        batch's context through set_context().  step_eta > 0 (the eta the steps run with, what sampling.check_eta
+        makes of a sampler and its `eta` keyword: 1 for sde2m): the stochastic step, whose noise the
+        stepper draws for step k from what set_noise() names"""
         return _graphed_or_eager(SAMPLER_GRAPH if graph is None else graph, device,
-                                 lambda: GraphedFastStep(self, params, B, device, ctx),
-                                 lambda: EagerFastStep(self, params, B, device, ctx),
+                                 lambda: GraphedFastStep(self, params, B, device, ctx, step_eta),
+                                 lambda: EagerFastStep(self, params, B, device, ctx, step_eta),
                                  "HIP-graph capture of the few-step sampler's step failed (%s: %s); sampling eagerly")
 
-    def fast_sample(self, params, z, ctx, sampler="dpm2m", steps=None, t_grid=None, graph=None, stepper=None):
-        """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m) over `steps` uniform steps or the explicit t_grid;
-        stepper: one from fast_stepper to re-use (its set_context re-targets it at this batch's ctx)"""
+    def fast_sample(self, params, z, ctx, sampler="dpm2m", steps=None, t_grid=None, graph=None, stepper=None, eta=0.0,
+                    noise=None):
+        """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m | sde2m) over `steps` uniform steps or the explicit
+        t_grid; stepper: one from fast_stepper to re-use (its set_context re-targets it at this batch's ctx).
+        eta: for ddim (0: the deterministic sampler).  noise (sde2m, ddim with eta > 0): the batch's step key -- step k
+        draws xi = randn under noise.fold_in(k) -- or a callable k -> xi [B, 3072]"""
         from . import sampling
+        step_eta = sampling.check_eta(sampler, eta)
         grid = sampling.time_grid(steps, t_grid)
         orders = sampling.step_orders(sampler, len(grid) - 1)
+        if step_eta > 0.0 and noise is None:
+            raise ValueError(f"fast_sample: {sampler!r} with eta = {step_eta} is stochastic and needs `noise`")
         B = z.shape[0]
         with torch.no_grad():
             if stepper is None:
-                stepper = self.fast_stepper(params, B, z.device, ctx, graph)
+                stepper = self.fast_stepper(params, B, z.device, ctx, graph, step_eta)
             elif not hasattr(stepper, "set_context"):
                 raise TypeError("fast_sample: a re-used stepper must take the batch's context (set_context): "
                                 f"{type(stepper).__name__} cannot be re-targeted")
+            elif getattr(stepper, "step_eta", 0.0) != step_eta:
+                raise ValueError(f"fast_sample: the stepper's steps run with eta = {getattr(stepper, 'step_eta', 0.0)}, "
+                                 f"this run asks for {step_eta}")
             else:
                 stepper.set_context(ctx)
+            if step_eta > 0.0:
+                stepper.set_noise(noise)
             return sampling.run(stepper, z.reshape(B, D).contiguous(), grid, orders)
 
 

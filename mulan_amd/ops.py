@@ -2187,6 +2187,26 @@ def fast_sampler_step(zt, net, gt, gs, mode, gprev=None, xprev=None, x0=True):
     return zs, xh
 
 
+def stochastic_sampler_step(z, net, g_t, g_s, mode, xi, eta, g_prev=None, x_prev=None):
+    """one step z_t -> z_s of DDIM with eta in [0, 1] (g_prev = x_prev = None) or, at second order, of its 2M form:
+    SDE-DPM-Solver++(2M) at eta = 1 (mulan_stochastic_sampler_step).  xi: one standard normal per element, shaped like
+    z; mode and the gamma layouts as fast_sampler_step.  Returns (z_s, x_hat_t)"""
+    if (g_prev is None) != (x_prev is None):
+        raise ValueError("stochastic_sampler_step: g_prev and x_prev go together (both None: first order)")
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"stochastic_sampler_step: eta must lie in [0, 1], got {eta!r}")
+    if xi is None or xi.numel() != z.numel():
+        raise ValueError("stochastic_sampler_step: xi must hold one standard normal per element of z")
+    z, net, g_t, g_s, xi = _c(z), _c(net), _c(g_t), _c(g_s), _c(xi)
+    g_prev, x_prev = (None, None) if g_prev is None else (_c(g_prev), _c(x_prev))
+    zs, xh = torch.empty_like(z), torch.empty_like(z)
+    per = z.numel() // g_t.numel()
+    call("mulan_stochastic_sampler_step", ptr(z), ptr(net), ptr(g_t), ptr(g_s), ptr(g_prev), ptr(x_prev), ptr(xi), eta,
+         ptr(zs), ptr(xh), z.numel(), int(mode), 0 if per == 1 else per, stream())
+    return zs, xh
+
+
 def decode_argmax(z0, g0):
     """uint8 argmax over the 256 decoder bins at z_0 / sqrt(1 - sigmoid(g_0)) (VDM.generate_x, sample_softmax=False)"""
     z0, g0 = _c(z0), _c(g0)

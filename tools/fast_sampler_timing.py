@@ -1,11 +1,12 @@
 """Wall time per batch of the samplers on one MI355X at the full CIFAR-10 configuration (random-init weights: the time
 does not depend on them).  Forms, alternated within one run after one untimed warm-up pass of each:
-  ancestral T = 1000 (replayed reverse step), ddim N = 50 (replayed), dpm2m N = 25 replayed, dpm2m N = 25 eager.
+  ancestral T = 1000 (replayed reverse step), ddim N = 50 (replayed), dpm2m N = 25 replayed, dpm2m N = 25 eager,
+  sde2m N = 25 replayed (the stochastic step: one randn and one more read of the latent's size per step).
 Each time is one batch from z_1 to the uint8 images (the loop plus generate_x) with the stepper built beforehand (what
 `python -m ldm.sample` pays per batch), between two device synchronisations.  One JSON line per timed batch, then a
 summary line (median ms per batch).
 
-    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3]
+    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3] [--few-step-only]
 """
 import argparse
 import json
@@ -22,6 +23,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--few-step-only", action="store_true", help="leave the 1000-step ancestral form out")
     args = ap.parse_args()
     import torch
     from mulan_amd.config import load_config_file
@@ -45,7 +47,8 @@ def main():
         ancestral = model.reverse_stepper(params, B, dev, emb, cond, ctx["coeffs"], T, graph=True)
         fast_replay = model.fast_stepper(params, B, dev, ctx, graph=True)
         fast_eager = model.fast_stepper(params, B, dev, ctx, graph=False)
-    assert type(fast_replay).__name__ == "GraphedFastStep"
+        sde_replay = model.fast_stepper(params, B, dev, ctx, graph=True, step_eta=1.0)
+    assert type(fast_replay).__name__ == "GraphedFastStep" and type(sde_replay).__name__ == "GraphedFastStep"
     assert type(getattr(ancestral, "__self__", None)).__name__ == "GraphedReverseStep"
 
     def run_ancestral():
@@ -54,13 +57,18 @@ def main():
             z = ancestral(i, z, rng)
         return model.generate_x(params, z, ctx["coeffs"])
 
-    def fast(sampler, N, stepper):
-        return lambda: model.generate_x(params, model.fast_sample(params, z1, ctx, sampler, N, stepper=stepper),
-                                        ctx["coeffs"])
+    def fast(sampler, N, stepper, noise=None):
+        return lambda: model.generate_x(params, model.fast_sample(params, z1, ctx, sampler, N, stepper=stepper,
+                                                                  noise=noise), ctx["coeffs"])
 
     forms = [("ancestral_T1000_replayed", run_ancestral), ("ddim_N50_replayed", fast("ddim", 50, fast_replay)),
-             ("dpm2m_N25_replayed", fast("dpm2m", 25, fast_replay)), ("dpm2m_N25_eager", fast("dpm2m", 25, fast_eager))]
+             ("dpm2m_N25_replayed", fast("dpm2m", 25, fast_replay)), ("dpm2m_N25_eager", fast("dpm2m", 25, fast_eager)),
+             ("sde2m_N25_replayed", fast("sde2m", 25, sde_replay, rng.fold_in(1)))]
+    if args.few_step_only:
+        forms = forms[1:]
     times = {name: [] for name, _ in forms}
+    print(json.dumps({"tool": "tools/fast_sampler_timing.py", "batch": B, "rounds": args.rounds,
+                      "few_step_only": args.few_step_only, "forms": [name for name, _ in forms]}), flush=True)
     with torch.no_grad():
         for name, fn in forms:                 # warm-up: one untimed batch of each form
             fn()
@@ -77,7 +85,9 @@ def main():
                 print(json.dumps({"round": r, "form": name, "batch": B, "ms_per_batch": round(ms, 2)}), flush=True)
     med = {k: round(statistics.median(v), 2) for k, v in times.items()}
     print(json.dumps({"summary": "median ms per batch", "batch": B, "rounds": args.rounds, **med,
-                      "ancestral_over_dpm2m_replayed": round(med["ancestral_T1000_replayed"] / med["dpm2m_N25_replayed"], 1),
+                      **({} if args.few_step_only else {"ancestral_over_dpm2m_replayed": round(
+                          med["ancestral_T1000_replayed"] / med["dpm2m_N25_replayed"], 1)}),
+                      "sde2m_over_dpm2m_replayed": round(med["sde2m_N25_replayed"] / med["dpm2m_N25_replayed"], 4),
                       "device": torch.cuda.get_device_name(0)}), flush=True)
     if packer is not None:
         packer.invalidate()
