@@ -482,6 +482,24 @@ int mulan_fast_sampler_step(const float* zt, const float* net, const float* gt, 
 int mulan_stochastic_sampler_step(const float* zt, const float* net, const float* gt, const float* gs,
                                   const float* gprev, const float* xprev, const float* xi, float eta, float* zs,
                                   float* x0, size_t n, int mode, int g_per_sample, mulan_stream_t stream);
+/* Inpainting with the few-step samplers (not in the reference): the known sub-pixels of a sampler state are overwritten
+ * with their own q(z_t | x), a closed form per element since the forward process is diagonal:
+ *   out[i] = mask[i] ? alpha(g_i) x[i] + sigma(g_i) xi[i] : z[i],  alpha = sqrt(sigmoid(-g)), sigma = sqrt(sigmoid(g)).
+ * x: the known image as mulan_encode_u8 makes it; mask: one byte per element, non-zero = known; xi: one standard normal
+ * per element (the kernel draws nothing), NULL = zeros, with the same bits as a buffer of zeros: a known element is
+ * then exactly the fp32 product alpha x.  An unknown element is z[i] bit for bit whatever x and xi hold there (NaN
+ * included).  out may be z.  gamma per element (g_per_sample = 0) or one value per g_per_sample consecutive elements.
+ * One thread per element (per float4 under the alignment and divisibility conditions of mulan_stochastic_sampler_step,
+ * the mask 4-byte aligned) over an exact-cover grid.  hipErrorInvalidValue for n == 0, a NULL z, x, mask, g or out, a
+ * negative g_per_sample or one that does not divide n, a grid of more than 2^31 - 1 blocks. */
+int mulan_inpaint_mix(const float* z, const float* x, const unsigned char* mask, const float* g, const float* xi,
+                      float* out, size_t n, int g_per_sample, mulan_stream_t stream);
+/* The forward transition q(z_t | z_s) for g_t >= g_s, the one whose Bayes inverse mulan_ancestral_step is:
+ *   zt[i] = sqrt(sigmoid(-g_t) / sigmoid(-g_s)) zs[i] + sqrt(sigmoid(g_t) c) xi[i],  c = -expm1(g_s - g_t).
+ * g_t == g_s returns zs bit for bit for any finite xi, the sign of a zero included.  zt may be zs.  Layouts, launch and refusals as
+ * mulan_inpaint_mix; xi is required. */
+int mulan_forward_jump(const float* zs, const float* gs, const float* gt, const float* xi, float* zt, size_t n,
+                       int g_per_sample, mulan_stream_t stream);
 /* out[r] = mean(x[r, :])  (VDM._get_score_model_gt, model_mulan_velocity.py:141-146) */
 int mulan_rowmean(const float* x, float* out, int rows, int cols, mulan_stream_t stream);
 

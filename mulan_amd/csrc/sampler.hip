@@ -363,3 +363,131 @@ MULAN_API int mulan_stochastic_sampler_step(const float* zt, const float* net, c
                        gprev, xprev, xi, eta, zs, x0, n, mode, g_per_sample);
   MULAN_CHECK_LAUNCH();
 }
+
+// ---- inpainting: the known sub-pixels of a sampler state, and the forward transition q(z_t | z_s) --------------------
+// MuLAN's forward process is diagonal, so q(z_t | x) of a known sub-pixel is a closed form per element with its own
+// gamma: the replacement method overwrites the known elements of the state after every step with
+//   alpha(g) x + sigma(g) xi,   alpha = sqrt(sigmoid(-g)), sigma = sqrt(sigmoid(g)),
+// and leaves the others as they are (a select, not a blend: what x and xi hold at an unknown element never reaches
+// out).  xi comes from a buffer (the kernel draws nothing); NULL reads as zeros through the same expression, so a zero
+// xi and a NULL xi give the same bits, and a known element is then exactly the fp32 product alpha x.
+// The forward jump s -> t (g_t >= g_s) is the transition whose Bayes inverse ancestral_step_kernel is:
+//   z_t = sqrt(sigmoid(-g_t) / sigmoid(-g_s)) z_s + sqrt(sigmoid(g_t) c) xi,   c = -expm1(g_s - g_t)
+// (sigma^2_{t|s} = sigma_t^2 c).  At g_t == g_s the ratio is x / x = 1 and c = 0: z_t == z_s for any finite xi, down to
+// the sign of a zero: a noise term that is zero is left out, since -0 + 0 would round to +0.
+// Both may run in place (out == z, zt == zs): every thread reads its own elements before it writes them.
+namespace {
+
+__device__ __forceinline__ float inpaint_mix_elem(float z, float x, unsigned m, float g, float xi) {
+  const float p = sqrtf(sigmoid_f(-g)) * x;
+  const float v = fmaf(sqrtf(sigmoid_f(g)), xi, p);
+  return m ? v : z;
+}
+
+__device__ __forceinline__ float forward_jump_elem(float z, float g_s, float g_t, float xi) {
+  const float as2 = sigmoid_f(-g_s), at2 = sigmoid_f(-g_t), c = -expm1f(g_s - g_t);
+  const float zr = sqrtf(at2 / as2) * z, nz = sqrtf(sigmoid_f(g_t) * c) * xi;
+  return nz == 0.f ? zr : zr + nz;
+}
+
+// one thread per float4 (VEC: n % 4 == 0, the float pointers 16-byte and the mask 4-byte aligned, g_per_sample % 4 == 0,
+// so a float4 has one 4-byte word of mask) or per element; the grid covers n exactly
+template <bool VEC>
+__global__ __launch_bounds__(256) void inpaint_mix_kernel(const float* z, const float* __restrict__ x,
+                                                          const unsigned char* __restrict__ mask,
+                                                          const float* __restrict__ g, const float* __restrict__ xi,
+                                                          float* out, size_t n, int g_per_sample) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (VEC) {
+    if (q >= n / 4) return;
+    const float4 z4 = reinterpret_cast<const float4*>(z)[q], x4 = reinterpret_cast<const float4*>(x)[q];
+    const float4 e4 = xi ? reinterpret_cast<const float4*>(xi)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const unsigned m4 = reinterpret_cast<const unsigned*>(mask)[q];
+    float4 g4;
+    if (g_per_sample) {
+      const float gv = g[(q * 4) / (size_t)g_per_sample];
+      g4 = make_float4(gv, gv, gv, gv);
+    } else {
+      g4 = reinterpret_cast<const float4*>(g)[q];
+    }
+    float4 o;
+    o.x = inpaint_mix_elem(z4.x, x4.x, m4 & 0xffu, g4.x, e4.x);
+    o.y = inpaint_mix_elem(z4.y, x4.y, m4 & 0xff00u, g4.y, e4.y);
+    o.z = inpaint_mix_elem(z4.z, x4.z, m4 & 0xff0000u, g4.z, e4.z);
+    o.w = inpaint_mix_elem(z4.w, x4.w, m4 & 0xff000000u, g4.w, e4.w);
+    reinterpret_cast<float4*>(out)[q] = o;
+  } else {
+    if (q >= n) return;
+    const size_t gi = g_per_sample ? q / (size_t)g_per_sample : q;
+    out[q] = inpaint_mix_elem(z[q], x[q], mask[q], g[gi], xi ? xi[q] : 0.f);
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void forward_jump_kernel(const float* zs, const float* __restrict__ gs,
+                                                           const float* __restrict__ gt, const float* __restrict__ xi,
+                                                           float* zt, size_t n, int g_per_sample) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (VEC) {
+    if (q >= n / 4) return;
+    const float4 z4 = reinterpret_cast<const float4*>(zs)[q], e4 = reinterpret_cast<const float4*>(xi)[q];
+    float4 gs4, gt4;
+    if (g_per_sample) {
+      const size_t gi = (q * 4) / (size_t)g_per_sample;
+      gs4 = make_float4(gs[gi], gs[gi], gs[gi], gs[gi]);
+      gt4 = make_float4(gt[gi], gt[gi], gt[gi], gt[gi]);
+    } else {
+      gs4 = reinterpret_cast<const float4*>(gs)[q];
+      gt4 = reinterpret_cast<const float4*>(gt)[q];
+    }
+    float4 o;
+    o.x = forward_jump_elem(z4.x, gs4.x, gt4.x, e4.x);
+    o.y = forward_jump_elem(z4.y, gs4.y, gt4.y, e4.y);
+    o.z = forward_jump_elem(z4.z, gs4.z, gt4.z, e4.z);
+    o.w = forward_jump_elem(z4.w, gs4.w, gt4.w, e4.w);
+    reinterpret_cast<float4*>(zt)[q] = o;
+  } else {
+    if (q >= n) return;
+    const size_t gi = g_per_sample ? q / (size_t)g_per_sample : q;
+    zt[q] = forward_jump_elem(zs[q], gs[gi], gt[gi], xi[q]);
+  }
+}
+
+bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+}  // namespace
+
+MULAN_API int mulan_inpaint_mix(const float* z, const float* x, const unsigned char* mask, const float* g,
+                                const float* xi, float* out, size_t n, int g_per_sample, hipStream_t stream) {
+  if (n == 0 || g_per_sample < 0 || !z || !x || !mask || !g || !out || (g_per_sample && n % (size_t)g_per_sample))
+    return (int)hipErrorInvalidValue;
+  const bool vec = n % 4 == 0 && (g_per_sample % 4) == 0 && aligned16(z) && aligned16(x) && aligned16(xi) &&
+                   aligned16(out) && aligned4(mask) && (g_per_sample || aligned16(g));
+  // every thread owns one float4 (or one element): the grid is the exact cover, refused where it does not fit a launch
+  const size_t nb = ((vec ? n / 4 : n) + 255) / 256;
+  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
+  if (vec)
+    hipLaunchKernelGGL(inpaint_mix_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, z, x, mask, g, xi, out, n,
+                       g_per_sample);
+  else
+    hipLaunchKernelGGL(inpaint_mix_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, z, x, mask, g, xi, out, n,
+                       g_per_sample);
+  MULAN_CHECK_LAUNCH();
+}
+
+MULAN_API int mulan_forward_jump(const float* zs, const float* gs, const float* gt, const float* xi, float* zt, size_t n,
+                                 int g_per_sample, hipStream_t stream) {
+  if (n == 0 || g_per_sample < 0 || !zs || !gs || !gt || !xi || !zt || (g_per_sample && n % (size_t)g_per_sample))
+    return (int)hipErrorInvalidValue;
+  const bool vec = n % 4 == 0 && (g_per_sample % 4) == 0 && aligned16(zs) && aligned16(xi) && aligned16(zt) &&
+                   (g_per_sample || (aligned16(gs) && aligned16(gt)));
+  const size_t nb = ((vec ? n / 4 : n) + 255) / 256;
+  if (nb > 0x7fffffffull) return (int)hipErrorInvalidValue;
+  if (vec)
+    hipLaunchKernelGGL(forward_jump_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, zs, gs, gt, xi, zt, n,
+                       g_per_sample);
+  else
+    hipLaunchKernelGGL(forward_jump_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, zs, gs, gt, xi, zt, n,
+                       g_per_sample);
+  MULAN_CHECK_LAUNCH();
+}

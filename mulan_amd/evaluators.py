@@ -74,31 +74,95 @@ class Experiment_Colab(Experiment_VDM):
         samples = self._embedding_samples(emb, self.rng, self._steps(T, sampler), sampler, eta)
         return ckpt_lib.generate_image_grids(samples).astype(np.uint8)
 
-    def sample_batches(self, keys, batch_size, embedding='deterministic', sampler='dpm2m', steps=25, eta=0.0):
+    KNOWN_NOISE_FOLD = 0x6B6E6F776E5F7869        # fold_in tag of a batch's known-region key: no step count reaches it
+
+    def _check_embedding(self, embedding, batch_size, inpaint):
+        """the refusals of sample_batches' `embedding`, before anything is drawn"""
+        mulan = hasattr(self.model, "deterministic_embedding")
+        if torch.is_tensor(embedding) or isinstance(embedding, np.ndarray):
+            if not inpaint:
+                raise ValueError("embedding must be 'deterministic' or 'random' where nothing is inpainted")
+            if not mulan:
+                raise ValueError("an explicit embedding needs a MuLAN model (model_vdm.VDM has no latent embedding)")
+            if tuple(embedding.shape) not in ((50,), (batch_size, 50)):
+                raise ValueError(f"an explicit embedding is [50] or [{batch_size}, 50], got {list(embedding.shape)}")
+            return
+        names = ('deterministic', 'random', 'encoder') if inpaint else ('deterministic', 'random')
+        if embedding not in names:
+            raise ValueError(f"embedding must be {' or '.join(repr(n) for n in names)}, got {embedding!r}")
+        if embedding != 'deterministic' and not mulan:
+            raise ValueError(f"embedding={embedding!r} needs a MuLAN model (model_vdm.VDM has no latent embedding)")
+        if embedding == 'encoder' and self.model.config.latent_type == 'gaussian':
+            raise ValueError("embedding='encoder' takes the hard top-k of the encoder's logits; latent_type 'gaussian' "
+                             "has none")
+
+    def _batch_embedding(self, embedding, k_e, batch_size, known=None, mask=None):
+        """the [B, 50] embedding of one batch (None: draw_samples takes the model's deterministic one)"""
+        from . import ops
+        if not isinstance(embedding, str):
+            emb = torch.as_tensor(embedding, dtype=torch.float32, device=self.device)
+            return emb.reshape(-1, 50).expand(batch_size, 50).contiguous()
+        if embedding == 'random':
+            return ops.topk_hard(k_e.normal((batch_size, 50), self.device), 15)[0]
+        if embedding == 'encoder':
+            keep = sampling.expand_mask(mask, batch_size, self.device).view(batch_size, 32, 32, 3) != 0
+            known = torch.as_tensor(known).to(self.device)
+            grey = torch.where(keep, known, torch.full_like(known, 128))
+            return ops.topk_hard(self.model.apply_encoder(self.params, grey), self.model.config.latent_k)[0]
+        return None
+
+    def sample_batches(self, keys, batch_size, embedding='deterministic', sampler='dpm2m', steps=25, eta=0.0, known=None,
+                       mask=None, resample=1):
         """uint8 [batch_size, 32, 32, 3] per key, each batch drawn from its key alone (the python -m ldm.sample CLI):
         key.split(3) -> (prior z_1 ~ sigma_prior N(0, I), random embedding logits, per-step noise); generate_x with
         key.fold_in(steps).  The per-step noise of the ancestral sampler, of sde2m and of ddim with eta > 0 comes from
         the third sub-key alone, folded with the step index, so neither z_1 nor the embedding shares a draw with it.
         embedding 'deterministic': model.deterministic_embedding (as sample_fn); 'random': the hard top-15 of random
         normal logits (as sample_randomly).  The few-step samplers re-use one stepper, re-targeted at every batch's
-        context."""
-        from . import ops
+        context.
+        known, mask (optional, one per key: uint8 [batch_size, 32, 32, 3] and a mask as draw_samples takes it; one
+        mask alone serves every batch): inpainting, `resample` passes per step.  The noise of the known region and of
+        the jumps comes from a fourth sub-key, key.fold_in(KNOWN_NOISE_FOLD), folded with the draw's own counter
+        (sampling.run_inpaint); the three sub-keys above and their draws are as without a mask.  Inpainting also takes
+        embedding 'encoder' (the hard top-k of apply_encoder on the images with the unknown pixels set to 128) or an
+        explicit k-hot tensor [50] or [batch_size, 50]."""
         sampling.check_eta(sampler, eta)
-        if embedding not in ('deterministic', 'random'):
-            raise ValueError(f"embedding must be 'deterministic' or 'random', got {embedding!r}")
-        mulan = hasattr(self.model, "deterministic_embedding")
-        if embedding == 'random' and not mulan:
-            raise ValueError("embedding='random' needs a MuLAN model (model_vdm.VDM has no latent embedding)")
+        keys = list(keys)
+        inpaint = sampling.check_inpaint(sampler, known, mask, resample)
+        if inpaint:
+            if torch.is_tensor(mask) or isinstance(mask, np.ndarray):
+                mask = [mask] * len(keys)
+            if len(known) != len(keys) or len(mask) != len(keys):
+                raise ValueError(f"{len(keys)} keys, but {len(known)} batches of known images and {len(mask)} masks")
+        self._check_embedding(embedding, batch_size, inpaint)
         out, stepper = [], None
-        for key in keys:
+        for b, key in enumerate(keys):
             k_z, k_e, k_s = key.split(3)
-            emb = None
-            if embedding == 'random':
-                emb, _ = ops.topk_hard(k_e.normal((batch_size, 50), self.device), 15)
+            kw = {}
+            if inpaint:
+                kw = dict(known=known[b], mask=mask[b], resample=resample, known_rng=key.fold_in(self.KNOWN_NOISE_FOLD))
+            emb = self._batch_embedding(embedding, k_e, batch_size, kw.get("known"), kw.get("mask"))
             x, stepper = self.draw_samples(self.params, batch_size, emb, k_z, k_s, key.fold_in(steps), sampler, steps,
-                                           prior_scale=float(self.config.model.sigma_prior), stepper=stepper, eta=eta)
+                                           prior_scale=float(self.config.model.sigma_prior), stepper=stepper, eta=eta,
+                                           **kw)
             out.append(x)
         return out
+
+    def inpaint(self, images, mask, embedding='deterministic', sampler='sde2m', steps=25, eta=0.0, resample=1, rng=None):
+        """uint8 [B, 32, 32, 3]: `images` (uint8 [B, 32, 32, 3]) with the sub-pixels outside `mask` (bool or uint8
+        [32, 32], [B, 32, 32] or [B, 32, 32, 3], True = keep) drawn by a few-step sampler (ddim with eta, dpm2m, sde2m)
+        that overwrites the kept ones after every step with their own alpha_t x + sigma_t eps (sampling.run_inpaint;
+        resample > 1: that many passes per step).  With argmax decoding (sample_softmax False) the kept sub-pixels come
+        back as they went in, with no paste-over.  embedding: 'deterministic', 'random', 'encoder' (MuLAN models: the hard
+        top-k of apply_encoder on the images with the unknown pixels set to 128) or a k-hot tensor [50] or [B, 50].
+        rng (default: the experiment's key) is folded with the rank and then split as sample_batches splits a batch's
+        key, so the same rng gives the same bytes."""
+        images = torch.as_tensor(images)
+        if images.dtype != torch.uint8 or images.dim() != 4 or tuple(images.shape[1:]) != (32, 32, 3):
+            raise ValueError(f"images are uint8 [B, 32, 32, 3], got {images.dtype} {list(images.shape)}")
+        key = (self.rng if rng is None else rng).fold_in(self.rank)
+        return self.sample_batches([key], images.shape[0], embedding, sampler, steps, eta, known=[images], mask=[mask],
+                                   resample=resample)[0]
 
     def test(self, loader):
         """Experiment_Colab.test: mean of the eval scalars over a loader"""

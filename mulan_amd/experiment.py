@@ -595,7 +595,7 @@ class Experiment_VDM(Experiment):
         return None
 
     def draw_samples(self, params, B, embedding, prior_rng, step_rng, decode_rng, sampler, steps, t_grid=None,
-                     prior_scale=1.0, stepper=None, eta=0.0):
+                     prior_scale=1.0, stepper=None, eta=0.0, known=None, mask=None, resample=1, known_rng=None):
         """One batch of B images, the loop every sampling entry point runs: z_1 = prior_scale * N(0, I) from prior_rng,
         `steps` steps of `sampler` under `embedding` (MuLAN models; None: model.deterministic_embedding) with the per-step
         noise of the ancestral sampler from step_rng (rng.fold_in(i) at step i), generate_x with decode_rng (needed by
@@ -603,8 +603,22 @@ class Experiment_VDM(Experiment):
         graph (model.GraphedReverseStep); ddim / dpm2m / sde2m (t_grid, if given, sets the step count):
         model.fast_sample, the stepper re-used when one is given (re-targeted at this batch's context) and returned for
         the next batch; sde2m and ddim with eta > 0 draw the noise of step k under step_rng.fold_in(k) as well.
+        known (uint8 [B, 32, 32, 3]) and mask (bool or uint8 [32, 32], [B, 32, 32] or [B, 32, 32, 3], True = keep; it
+        is broadcast to one byte per sub-pixel): inpainting with the few-step samplers (sampling.run_inpaint), `resample`
+        passes per step.  The noise of the known region and of the jumps comes from known_rng alone, a key that neither
+        z_1 nor the step noise uses: draw j under known_rng.fold_in(j).  With argmax decoding the kept sub-pixels of
+        the result are the input's, with no paste-over.
         -> (uint8 [B, 32, 32, 3], stepper or None)"""
         step_eta = sampling.check_eta(sampler, eta)          # what the steps run with: 1 for sde2m
+        inpaint = sampling.check_inpaint(sampler, known, mask, resample)
+        if inpaint:
+            if known_rng is None:
+                raise ValueError("draw_samples: inpainting needs known_rng, the key of the known region's noise")
+            known = torch.as_tensor(known)
+            if known.dtype != torch.uint8 or tuple(known.shape) != (B, 32, 32, 3):
+                raise ValueError(f"draw_samples: known is uint8 [{B}, 32, 32, 3], got {known.dtype} "
+                                 f"{list(known.shape)}")
+            mask = sampling.expand_mask(mask, B, self.device)
         packer = self._packer_for(params)
         conditioning = torch.zeros(B, dtype=torch.uint8, device=self.device)
         mulan = hasattr(self.model, "reverse_stepper")
@@ -630,9 +644,16 @@ class Experiment_VDM(Experiment):
                 else:
                     ctx = self.model.fast_context(params, embedding if mulan else None, conditioning)
                     if stepper is None:
-                        stepper = self.model.fast_stepper(params, B, self.device, ctx, step_eta=step_eta)
+                        stepper = self.model.fast_stepper(params, B, self.device, ctx, step_eta=step_eta,
+                                                          inpaint=inpaint)
+                    kw = {}
+                    if inpaint:
+                        from . import ops
+                        kw = dict(known=ops.encode_u8(known.to(self.device)).reshape(B, 3072), mask=mask,
+                                  resample=resample, known_noise=known_rng)
                     z = self.model.fast_sample(params, z, ctx, sampler, None if t_grid is not None else steps, t_grid,
-                                               stepper=stepper, eta=eta, noise=step_rng if step_eta > 0.0 else None)
+                                               stepper=stepper, eta=eta, noise=step_rng if step_eta > 0.0 else None,
+                                               **kw)
                     coeffs = ctx.get("coeffs")
                 samples = self.model.generate_x(params, z, coeffs, rng=decode_rng)
             finally:

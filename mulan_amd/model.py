@@ -247,21 +247,68 @@ def _fill_step_noise(buf, noise, k):
     return buf
 
 
-class EagerFastStep:
+def _fill_known_noise(buf, noise, j):
+    """draw j of an inpainting run -- the noise of the known region at a mix, or of a jump -- into buf [B, 3072]:
+    `noise` is the batch's known-region key (ops.randn under key.fold_in(j)) or a callable j -> xi;
+    j = sampling.ZERO_NOISE: zeros (the mix of the last step)"""
+    if j < 0:
+        return buf.zero_()
+    if noise is None:
+        raise RuntimeError("inpainting needs the batch's known-region noise (set_known: a Key, or a callable j -> xi)")
+    if callable(noise):
+        buf.copy_(noise(j).reshape(buf.shape))
+    else:
+        ops.randn(None, noise.fold_in(j).v, 0, buf.device, out=buf)
+    return buf
+
+
+class _KnownBuffers:
+    """What an inpainting stepper keeps per batch in static buffers: the known image x [B, 3072] (as ops.encode_u8
+    gives it), the mask (one byte per sub-pixel, non-zero = keep) and the noise of the known region for the mix;
+    set_known() fills the first two and names the key (or callable) that noise, and a jump's, is drawn from."""
+
+    def _init_known(self, B, device, inpaint):
+        self.inpaint, self.known_noise = bool(inpaint), None
+        self.known = self.mask = self.kxi = None
+        if self.inpaint:
+            f32 = dict(device=device, dtype=torch.float32)
+            self.known, self.mask = torch.zeros((B, D), **f32), torch.zeros((B, D), device=device, dtype=torch.uint8)
+            self.kxi = torch.zeros((B, D), **f32)
+
+    def set_known(self, known, mask, noise=None):
+        """this batch's known image and mask (B x 3072 elements each) and its known-region noise"""
+        if not self.inpaint:
+            raise ValueError("this stepper was built without a mask (fast_stepper(..., inpaint=True) builds one with)")
+        if known.numel() != self.known.numel() or mask.numel() != self.mask.numel():
+            raise ValueError(f"the known image and the mask hold {tuple(self.known.shape)} elements each, got "
+                             f"{tuple(known.shape)} and {tuple(mask.shape)}")
+        self.known.copy_(known.reshape(self.known.shape))
+        self.mask.copy_(mask.reshape(self.mask.shape))
+        self.known_noise = noise
+
+    def _check_mix(self, mix):
+        if (mix is not None) != self.inpaint:
+            raise ValueError("a stepper built with a mask mixes after every step, and one built without never does")
+
+
+class EagerFastStep(_KnownBuffers):
     """The eager form of GraphedFastStep (MULAN_SAMPLER_GRAPH=0, or a failed capture): sampling.EagerStepper over the
     model's network and schedule, reading the context through this object so that set_context() re-targets it at the
     next batch like the replayed stepper.  step_eta > 0 (sampling.check_eta): the stochastic step on the noise
-    set_noise() names."""
+    set_noise() names.  inpaint: the stepper of an inpainting run (sampling.run_inpaint) on what set_known() holds."""
 
-    def __init__(self, model, params, B, device, ctx, step_eta=0.0):
+    def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False):
         from . import sampling
         self.ctx, self.step_eta, self.noise = ctx, float(step_eta), None
+        self._init_known(B, device, inpaint)
         times = lambda t: torch.full((B,), float(np.float32(t)), device=device, dtype=torch.float32)
         gamma_fn = lambda t: model._fast_gamma(params, self.ctx, times(t))
         net_fn = lambda z, t: model._fast_net(params, z.reshape(B, D), gamma_fn(t), self.ctx).view(z.shape)
         self.xi = torch.zeros((B, D), device=device, dtype=torch.float32) if self.step_eta > 0.0 else None
         noise_fn = (lambda k: _fill_step_noise(self.xi, self.noise, k)) if self.step_eta > 0.0 else None
-        self._make = lambda: sampling.EagerStepper(net_fn, gamma_fn, model._fast_mode(), self.step_eta, noise_fn)
+        known_fn = (lambda j: _fill_known_noise(self.kxi, self.known_noise, j)) if self.inpaint else None
+        self._make = lambda: sampling.EagerStepper(net_fn, gamma_fn, model._fast_mode(), self.step_eta, noise_fn,
+                                                   self.known, self.mask, known_fn)
         self._step = self._make()
 
     def set_context(self, ctx):
@@ -272,11 +319,18 @@ class EagerFastStep:
     def set_noise(self, noise):
         self.noise = noise
 
-    def __call__(self, z, t, s, order, k=None):
-        return self._step(z, t, s, order, k)
+    def mix(self, z, t, j):
+        return self._step.mix(z, t, j)
+
+    def jump(self, z, s, t, j):
+        return self._step.jump(z, s, t, j)
+
+    def __call__(self, z, t, s, order, k=None, mix=None):
+        self._check_mix(mix)
+        return self._step(z, t, s, order, k, mix)
 
 
-class GraphedFastStep:
+class GraphedFastStep(_KnownBuffers):
     """One step of the deterministic few-step samplers (DDIM / DPM-Solver++(2M), mulan_amd.sampling) captured as a HIP
     graph and replayed N times.  What changes from step to step reaches the kernels through static buffers written
     before each replay: z_t, the two times t, s and the history (the previous step's gamma and x_hat, copied from the
@@ -289,11 +343,18 @@ class GraphedFastStep:
     step_eta > 0 captures the stochastic step (DDIM with eta, SDE-DPM-Solver++(2M)) instead: its noise xi is one more static
     buffer, filled before each replay by the Philox call of the eager stepper (_fill_step_noise, the pattern of
     GraphedReverseStep.step); step_eta is an argument of the captured launch, so a stepper serves the one it was built
-    for."""
+    for.
+    inpaint captures the mix behind the step kernel (mulan_inpaint_mix at gamma_s): the known image, the mask and the
+    known region's noise are static buffers, the first two set per batch (set_known), the noise filled before each
+    replay (_fill_known_noise; zeros for the last step, which the kernel reads as it reads a NULL xi).  The mix of z_1
+    and the jumps of the resampling are eager launches between replays, the jump on a static noise buffer of its own."""
 
-    def __init__(self, model, params, B, device, ctx, step_eta=0.0):
+    def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False):
         self.B, self.step_eta, self.noise = B, float(step_eta), None
+        self.model, self.params = model, params
+        self._init_known(B, device, inpaint)
         f32 = dict(device=device, dtype=torch.float32)
+        self.jxi = torch.zeros((B, D), **f32) if self.inpaint else None       # the noise of a jump
         self.ctx = {k: (None if v is None else tuple(c.detach().clone() for c in v) if isinstance(v, tuple)
                         else v.detach().clone()) for k, v in ctx.items()}
         self.z_in, self.x_prev = torch.zeros((B, D), **f32), torch.zeros((B, D), **f32)
@@ -301,7 +362,7 @@ class GraphedFastStep:
         self.g_prev = torch.full(model._fast_gamma_shape(B), float("nan"), **f32)
         self.xi = torch.zeros((B, D), **f32) if self.step_eta > 0.0 else None
         run = lambda: model._fast_step(params, self.z_in, self.t, self.s, self.g_prev, self.x_prev, self.ctx, self.xi,
-                                       self.step_eta)
+                                       self.step_eta, self.known, self.mask, self.kxi)
         with torch.no_grad():
             self.graph, (self.z_out, self.x_out, self.g_out) = _capture(run)
         self.has_history = False
@@ -319,11 +380,28 @@ class GraphedFastStep:
     def set_noise(self, noise):
         self.noise = noise
 
-    def __call__(self, z, t, s, order, k=None):
+    def _gamma_at(self, buf, t):
+        buf.fill_(float(np.float32(t)))
+        return self.model._fast_gamma(self.params, self.ctx, buf)
+
+    def mix(self, z, t, j):
+        g = self._gamma_at(self.t, t)
+        _fill_known_noise(self.kxi, self.known_noise, j)
+        return ops.inpaint_mix(z.reshape(self.B, D), self.known, self.mask, g, self.kxi).view(z.shape)
+
+    def jump(self, z, s, t, j):
+        g_s, g_t = self._gamma_at(self.s, s), self._gamma_at(self.t, t)
+        _fill_known_noise(self.jxi, self.known_noise, j)
+        return ops.forward_jump(z.reshape(self.B, D), g_s, g_t, self.jxi).view(z.shape)
+
+    def __call__(self, z, t, s, order, k=None, mix=None):
+        self._check_mix(mix)
         if order == 2 and not self.has_history:
             raise RuntimeError("a second-order step needs the history of a previous step")
         if self.xi is not None:
             _fill_step_noise(self.xi, self.noise, k)
+        if mix is not None:
+            _fill_known_noise(self.kxi, self.known_noise, mix)
         self.z_in.copy_(z.reshape(self.B, D))
         self.t.fill_(float(np.float32(t)))
         self.s.fill_(float(np.float32(s)))
@@ -660,9 +738,11 @@ class _VDMBase:
         return drift, ops.ode_div(gx.reshape(B, D), gt, gp, hutch, mode, div_out)
 
     # ---- few-step samplers (mulan_amd.sampling; not in the reference) ----------------------------------------------
-    def _fast_step(self, params, z, t, s, g_prev, x_prev, ctx, xi=None, step_eta=0.0):
+    def _fast_step(self, params, z, t, s, g_prev, x_prev, ctx, xi=None, step_eta=0.0, known=None, mask=None,
+                   known_xi=None):
         """the device work of one step t -> s: (z_s, x_hat_t, gamma_t); g_prev / x_prev None: first order; xi [B, 3072]
-        with step_eta > 0: the stochastic step on that noise"""
+        with step_eta > 0: the stochastic step on that noise; known / mask [B, 3072] (inpainting): the known sub-pixels
+        of z_s are then replaced by alpha_s known + sigma_s known_xi (known_xi None: zero noise)"""
         g_t = self._fast_gamma(params, ctx, t)
         g_s = self._fast_gamma(params, ctx, s)
         net = self._fast_net(params, z, g_t, ctx)
@@ -671,46 +751,69 @@ class _VDMBase:
                                                       x_prev)
         else:
             z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, self._fast_mode(), g_prev, x_prev)
+        if mask is not None:
+            z_s = ops.inpaint_mix(z_s, known, mask, g_s, known_xi, out=z_s)
         return z_s, x0, g_t
 
-    def fast_stepper(self, params, B, device, ctx, graph=None, step_eta=0.0):
+    def fast_stepper(self, params, B, device, ctx, graph=None, step_eta=0.0, inpaint=False):
         """-> step(z, t, s, order[, k]) of the few-step samplers: a replayed HIP graph (GraphedFastStep) by default
         (MULAN_SAMPLER_GRAPH), eager where the capture fails (logged) or graph=False (EagerFastStep); both take the next
         batch's context through set_context().  step_eta > 0 (the eta the steps run with, what sampling.check_eta
         makes of a sampler and its `eta` keyword: 1 for sde2m): the stochastic step, whose noise the
-        stepper draws for step k from what set_noise() names"""
+        stepper draws for step k from what set_noise() names.  inpaint: a stepper that replaces the known sub-pixels
+        after every step, on the image, mask and known-region noise of set_known(); it serves inpainting runs only,
+        and a stepper built without serves none"""
         return _graphed_or_eager(SAMPLER_GRAPH if graph is None else graph, device,
-                                 lambda: GraphedFastStep(self, params, B, device, ctx, step_eta),
-                                 lambda: EagerFastStep(self, params, B, device, ctx, step_eta),
+                                 lambda: GraphedFastStep(self, params, B, device, ctx, step_eta, inpaint),
+                                 lambda: EagerFastStep(self, params, B, device, ctx, step_eta, inpaint),
                                  "HIP-graph capture of the few-step sampler's step failed (%s: %s); sampling eagerly")
 
     def fast_sample(self, params, z, ctx, sampler="dpm2m", steps=None, t_grid=None, graph=None, stepper=None, eta=0.0,
-                    noise=None):
+                    noise=None, known=None, mask=None, resample=1, known_noise=None):
         """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m | sde2m) over `steps` uniform steps or the explicit
         t_grid; stepper: one from fast_stepper to re-use (its set_context re-targets it at this batch's ctx).
         eta: for ddim (0: the deterministic sampler).  noise (sde2m, ddim with eta > 0): the batch's step key -- step k
-        draws xi = randn under noise.fold_in(k) -- or a callable k -> xi [B, 3072]"""
+        draws xi = randn under noise.fold_in(k) -- or a callable k -> xi [B, 3072].
+        known (fp32 [B, 3072], the image as ops.encode_u8 gives it) and mask (uint8 or bool [B, 3072], non-zero = keep):
+        inpainting (sampling.run_inpaint) with `resample` passes per step.  known_noise: the batch's known-region key --
+        draw j of the run (the noise of the known region at a mix, or of a jump; run_inpaint states which j is drawn
+        when) is randn under known_noise.fold_in(j) -- or a callable j -> xi [B, 3072].  It is a key of its own: step k
+        keeps drawing under noise.fold_in(k), and round r of a resampled step k under noise.fold_in(k + r N)"""
         from . import sampling
         step_eta = sampling.check_eta(sampler, eta)
+        inpaint = sampling.check_inpaint(sampler, known, mask, resample)
+        B = z.shape[0]
+        if inpaint:
+            if known.dtype != torch.float32 or tuple(known.shape) != (B, D):
+                raise ValueError(f"fast_sample: known is the encoded image, fp32 [{B}, {D}]; got {known.dtype} "
+                                 f"{tuple(known.shape)}")
+            if mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (B, D):
+                raise ValueError(f"fast_sample: mask is uint8 or bool [{B}, {D}]; got {mask.dtype} {tuple(mask.shape)}")
+            if known_noise is None:
+                raise ValueError("fast_sample: inpainting needs `known_noise` (the batch's known-region key)")
         grid = sampling.time_grid(steps, t_grid)
         orders = sampling.step_orders(sampler, len(grid) - 1)
         if step_eta > 0.0 and noise is None:
             raise ValueError(f"fast_sample: {sampler!r} with eta = {step_eta} is stochastic and needs `noise`")
-        B = z.shape[0]
         with torch.no_grad():
             if stepper is None:
-                stepper = self.fast_stepper(params, B, z.device, ctx, graph, step_eta)
+                stepper = self.fast_stepper(params, B, z.device, ctx, graph, step_eta, inpaint)
             elif not hasattr(stepper, "set_context"):
                 raise TypeError("fast_sample: a re-used stepper must take the batch's context (set_context): "
                                 f"{type(stepper).__name__} cannot be re-targeted")
             elif getattr(stepper, "step_eta", 0.0) != step_eta:
                 raise ValueError(f"fast_sample: the stepper's steps run with eta = {getattr(stepper, 'step_eta', 0.0)}, "
                                  f"this run asks for {step_eta}")
+            elif bool(getattr(stepper, "inpaint", False)) != inpaint:
+                raise ValueError("fast_sample: the stepper was built %s a mask, this run comes %s one"
+                                 % (("without", "with") if inpaint else ("with", "without")))
             else:
                 stepper.set_context(ctx)
             if step_eta > 0.0:
                 stepper.set_noise(noise)
-            return sampling.run(stepper, z.reshape(B, D).contiguous(), grid, orders)
+            if inpaint:
+                stepper.set_known(known, mask, known_noise)
+            return sampling.run(stepper, z.reshape(B, D).contiguous(), grid, orders, resample)
 
 
 class MulanVDM(_VDMBase):

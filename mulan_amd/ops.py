@@ -2207,6 +2207,48 @@ def stochastic_sampler_step(z, net, g_t, g_s, mode, xi, eta, g_prev=None, x_prev
     return zs, xh
 
 
+def inpaint_mix(z, x, mask, g, xi=None, out=None):
+    """the known sub-pixels of a sampler state z replaced by their q(z_t | x) (mulan_inpaint_mix):
+    mask ? alpha(g) x + sigma(g) xi : z.  x: the known image as encode_u8 gives it, shaped like z; mask: uint8 (or
+    bool), one byte per element, non-zero = known; g per element or per sample ([B]); xi: one standard normal per
+    element, None = zeros (a known element is then exactly alpha x).  Returns a new tensor shaped like z (out: the
+    tensor to write, which may be z)"""
+    if x.numel() != z.numel() or mask.numel() != z.numel() or (xi is not None and xi.numel() != z.numel()):
+        raise ValueError("inpaint_mix: x, mask and xi hold one value per element of z")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+    if mask.dtype != torch.uint8:
+        raise ValueError(f"inpaint_mix: the mask is bool or uint8, got {mask.dtype}")
+    if g.numel() == 0 or z.numel() % g.numel():
+        raise ValueError("inpaint_mix: gamma is per element or per sample")
+    z, x, mask, g = _c(z), _c(x), _c(mask), _c(g)
+    xi = None if xi is None else _c(xi)
+    if out is None:
+        out = torch.empty_like(z)
+    elif (out.shape != z.shape or out.dtype != torch.float32 or out.device != z.device or not out.is_contiguous()):
+        raise ValueError("inpaint_mix: out is a contiguous fp32 tensor shaped like z, on its device")
+    per = z.numel() // g.numel()
+    call("mulan_inpaint_mix", ptr(z), ptr(x), ptr(mask), ptr(g), ptr(xi), ptr(out), z.numel(), 0 if per == 1 else per,
+         stream())
+    return out
+
+
+def forward_jump(z_s, g_s, g_t, xi):
+    """z_t ~ q(z_t | z_s) for g_t >= g_s on the noise xi (mulan_forward_jump):
+    sqrt(sigmoid(-g_t) / sigmoid(-g_s)) z_s + sqrt(sigmoid(g_t) (1 - e^(g_s - g_t))) xi; gamma per element or per
+    sample ([B]); xi: one standard normal per element.  Returns a new tensor shaped like z_s"""
+    if xi is None or xi.numel() != z_s.numel():
+        raise ValueError("forward_jump: xi must hold one standard normal per element of z_s")
+    if g_s.numel() == 0 or g_s.numel() != g_t.numel() or z_s.numel() % g_s.numel():
+        raise ValueError("forward_jump: gamma is per element or per sample, the same layout at s and at t")
+    z_s, g_s, g_t, xi = _c(z_s), _c(g_s), _c(g_t), _c(xi)
+    z_t = torch.empty_like(z_s)
+    per = z_s.numel() // g_s.numel()
+    call("mulan_forward_jump", ptr(z_s), ptr(g_s), ptr(g_t), ptr(xi), ptr(z_t), z_s.numel(), 0 if per == 1 else per,
+         stream())
+    return z_t
+
+
 def decode_argmax(z0, g0):
     """uint8 argmax over the 256 decoder bins at z_0 / sqrt(1 - sigmoid(g_0)) (VDM.generate_x, sample_softmax=False)"""
     z0, g0 = _c(z0), _c(g0)

@@ -12,6 +12,15 @@ replayed as a HIP graph).  A stochastic step (eta > 0) is the HIP kernel mulan_s
 (ops.stochastic_sampler_step) on one standard normal per element, which the loop hands over step by step
 (noise_fn(k)); eta = 0 keeps the deterministic kernel and its bits.  Second order at 0 < eta < 1 is an interpolation
 of dpm2m and sde2m and no named method; no sampler here asks for it.
+
+Inpainting (the replacement method, with RePaint-style resampling): given a known image x and a mask, the known
+sub-pixels of the state are overwritten with their own q(z_t | x) = alpha_t x + sigma_t eps -- a closed form per element,
+by the same diagonal argument -- before the first step (at t = 1) and after every step t -> s (at gamma_s;
+ops.inpaint_mix, mulan_inpaint_mix).  The last mix (s = 0) takes zero noise, so the known sub-pixels of z_0 are exactly
+alpha_0 x and decode back to the input's integers.  With resample = U > 1 every step but the last is followed by U - 1
+rounds of: the forward transition q(z_t | z_s) back to t on fresh noise (ops.forward_jump, mulan_forward_jump), the step
+t -> s again at first order, and the mix; the history a repeated step leaves serves the next step as usual.
+The noise of the known region and of the jumps is known_noise_fn(j), j a counter of its own (run_inpaint states the law).
 """
 import numpy as np
 import torch
@@ -86,26 +95,127 @@ def f32(t):
     return float(np.float32(t))
 
 
+ZERO_NOISE = -1                     # the `mix` argument of an inpainting step whose mix takes no noise (the last step)
+
+
+def check_resample(resample):
+    """the passes per step of an inpainting run: an integer >= 1 (1: no resampling)"""
+    try:
+        ok = not isinstance(resample, bool) and int(resample) == resample and resample >= 1
+    except (TypeError, ValueError, OverflowError):          # (None, a string, NaN, an infinity)
+        ok = False
+    if not ok:
+        raise ValueError(f"resample must be an integer >= 1, got {resample!r}")
+    return int(resample)
+
+
+def check_inpaint(sampler, known, mask, resample=1):
+    """-> whether the run inpaints: the known image and the mask go together, belong to the few-step samplers, and
+    resample > 1 needs them"""
+    check_sampler(sampler)
+    resample = check_resample(resample)
+    if (known is None) != (mask is None):
+        raise ValueError("inpainting needs the known image and its mask together")
+    if mask is None:
+        if resample != 1:
+            raise ValueError("resample applies to inpainting (a known image and a mask)")
+        return False
+    if sampler not in FAST_SAMPLERS:
+        raise ValueError(f"inpainting runs with the few-step samplers ({', '.join(FAST_SAMPLERS)}); "
+                         f"the {sampler!r} sampler takes no mask")
+    return True
+
+
+def mask_from_spec(spec):
+    """a mask named in words -> bool [32, 32] (True = keep):
+    'box:y0,x0,y1,x1'  the rows y0 .. y1 - 1 and columns x0 .. x1 - 1 are unknown, the rest is kept
+    'half:left|right|top|bottom'  that half of the image is kept"""
+    kind, _, arg = str(spec).partition(":")
+    keep = np.ones((32, 32), dtype=bool)
+    if kind == "box":
+        try:
+            y0, x0, y1, x1 = (int(v) for v in arg.split(","))
+        except ValueError:
+            raise ValueError(f"mask {spec!r}: box takes four integers y0,x0,y1,x1") from None
+        if not (0 <= y0 < y1 <= 32 and 0 <= x0 < x1 <= 32):
+            raise ValueError(f"mask {spec!r}: the box needs 0 <= y0 < y1 <= 32 and 0 <= x0 < x1 <= 32")
+        keep[y0:y1, x0:x1] = False
+        return keep
+    if kind == "half" and arg in ("left", "right", "top", "bottom"):
+        keep[:] = False
+        keep[{"left": np.s_[:, :16], "right": np.s_[:, 16:], "top": np.s_[:16], "bottom": np.s_[16:]}[arg]] = True
+        return keep
+    raise ValueError(f"mask {spec!r}: expected box:y0,x0,y1,x1 or half:left|right|top|bottom")
+
+
+def expand_mask(mask, B, device=None):
+    """a mask of shape [32, 32], [B, 32, 32] or [B, 32, 32, 3] (bool or uint8, non-zero = keep; array or tensor) -> uint8
+    [B, 3072], one byte (0 / 1) per sub-pixel"""
+    m = mask if torch.is_tensor(mask) else torch.tensor(np.asarray(mask))       # (a copy: the array may be read-only)
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"the mask is bool or uint8, got {m.dtype}")
+    shape = tuple(m.shape)
+    if shape == (32, 32):
+        m = m[None, :, :, None]
+    elif shape == (B, 32, 32):
+        m = m[:, :, :, None]
+    elif shape != (B, 32, 32, 3):
+        raise ValueError(f"the mask has shape [32, 32], [{B}, 32, 32] or [{B}, 32, 32, 3], got {list(shape)}")
+    m = (m != 0).expand(B, 32, 32, 3).reshape(B, 3072).to(torch.uint8)
+    return m.contiguous() if device is None else m.to(device).contiguous()
+
+
 class EagerStepper:
     """One solver step at a time through ops.fast_sampler_step, the history in tensors of its own.
     net_fn(z, t) -> network output shaped like z; gamma_fn(t) -> gamma at the (fp32) time t, per element (shaped like
     z) or per sample ([B]).  With step_eta > 0 (check_eta) the step is ops.stochastic_sampler_step on xi = noise_fn(k),
-    one standard normal per element for step k (the fifth argument of the call)."""
+    one standard normal per element for step k (the fifth argument of the call).
+    known / mask (both or neither; shaped like z, the image as ops.encode_u8 gives it and one byte per element): the
+    inpainting stepper, whose steps end with the mix at gamma_s on known_noise_fn(j) (the call's `mix` argument names
+    j; ZERO_NOISE: the noiseless mix of the last step), and which has mix() for z_1 and jump() for the resampling."""
 
-    def __init__(self, net_fn, gamma_fn, mode, step_eta=0.0, noise_fn=None):
+    def __init__(self, net_fn, gamma_fn, mode, step_eta=0.0, noise_fn=None, known=None, mask=None, known_noise_fn=None):
         self.net_fn, self.gamma_fn, self.mode = net_fn, gamma_fn, int(mode)
         self.step_eta, self.noise_fn = float(step_eta), noise_fn
         if self.step_eta > 0.0 and noise_fn is None:
             raise ValueError("a stochastic step (step_eta > 0) needs noise_fn(k) -> xi")
         self.g_prev = self.x_prev = None
         self._g = None              # (t, gamma(t)) of the last step's s: the next step's t
+        self.known = self.mask = self.known_noise_fn = None
+        if known is not None or mask is not None or known_noise_fn is not None:
+            self.set_known(known, mask, known_noise_fn)
+
+    @property
+    def inpaint(self):
+        return self.mask is not None
+
+    def set_known(self, known, mask, known_noise_fn):
+        if known is None or mask is None:
+            raise ValueError("inpainting needs the known image and its mask together")
+        if known_noise_fn is None:
+            raise ValueError("inpainting needs known_noise_fn(j) -> the noise of the known region and of the jumps")
+        self.known, self.mask, self.known_noise_fn = known, mask, known_noise_fn
 
     def _gamma(self, t):
         if self._g is not None and self._g[0] == t:
             return self._g[1]
         return self.gamma_fn(t)
 
-    def __call__(self, z, t, s, order, k=None):
+    def _known_xi(self, j):
+        return None if j == ZERO_NOISE else self.known_noise_fn(j)
+
+    def mix(self, z, t, j):
+        """the known sub-pixels of z replaced by alpha_t x + sigma_t known_noise_fn(j)"""
+        return ops.inpaint_mix(z, self.known, self.mask, self._gamma(f32(t)), self._known_xi(j))
+
+    def jump(self, z, s, t, j):
+        """z_t ~ q(z_t | z_s = z) on known_noise_fn(j)"""
+        s, t = f32(s), f32(t)
+        return ops.forward_jump(z, self._gamma(s), self.gamma_fn(t), self.known_noise_fn(j))
+
+    def __call__(self, z, t, s, order, k=None, mix=None):
+        if (mix is not None) != self.inpaint:
+            raise ValueError("an inpainting stepper mixes after every step, and no other stepper does")
         t, s = f32(t), f32(s)
         g_t = self._gamma(t)
         g_s = self.gamma_fn(s)
@@ -120,25 +230,68 @@ class EagerStepper:
                                                       *hist)
         else:
             z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, self.mode, *hist)
+        if mix is not None:
+            z_s = ops.inpaint_mix(z_s, self.known, self.mask, g_s, self._known_xi(mix), out=z_s)
         self.g_prev, self.x_prev, self._g = g_t, x0, (s, g_s)
         return z_s
 
 
-def run(stepper, z, grid, orders):
+def run(stepper, z, grid, orders, resample=1, known=None, mask=None, known_noise_fn=None):
     """the solver loop: stepper(z, t, s, order, k) -> z_s along the grid; the step's index k selects the noise of a
-    stochastic step"""
+    stochastic step.  known / mask / known_noise_fn: handed to the stepper (set_known); a stepper that inpaints runs
+    run_inpaint with `resample`"""
     assert len(orders) == len(grid) - 1
+    if known is not None or mask is not None:
+        stepper.set_known(known, mask, known_noise_fn)
+    if getattr(stepper, "inpaint", False):
+        return run_inpaint(stepper, z, grid, orders, resample)
+    if check_resample(resample) != 1:
+        raise ValueError("resample applies to inpainting (a known image and a mask)")
     for k, order in enumerate(orders):
         z = stepper(z, grid[k], grid[k + 1], order, k)
     return z
 
 
-def sample(net_fn, gamma_fn, z, mode, sampler="dpm2m", steps=None, t_grid=None, eta=0.0, noise_fn=None):
+def run_inpaint(stepper, z, grid, orders, resample=1):
+    """the solver loop of an inpainting stepper: z_1 mixed at t = 1; every step t -> s followed by the mix at gamma_s
+    (inside the stepper's call), the last one with zero noise; with resample = U > 1 every step but the last is followed
+    by U - 1 rounds of jump s -> t, the step t -> s again at first order, and the mix.
+    Noise: the known region's and the jumps' noise is the stepper's known_noise_fn(j).  A deterministic run (step_eta = 0
+    and U = 1) uses j = 0 at every mix, so the known region follows alpha_t x + sigma_t eps with one eps: a consistent
+    trajectory for an ODE solver.  Otherwise every mix and every jump takes the next j = 0, 1, 2, ... in the order they
+    run (the mix of z_1 first; per round the jump, then the mix).  Round r = 1 .. U - 1 of step k draws the noise of its
+    stochastic step under the step index k + r N (N steps), which no first pass uses."""
+    U, N = check_resample(resample), len(orders)
+    fresh = U > 1 or getattr(stepper, "step_eta", 0.0) > 0.0
+    count = [0]
+
+    def draw():
+        j = count[0]
+        count[0] += int(fresh)
+        return j
+    z = stepper.mix(z, grid[0], draw())
+    for k, order in enumerate(orders):
+        t, s, last = grid[k], grid[k + 1], k == N - 1
+        z = stepper(z, t, s, order, k, ZERO_NOISE if last else draw())
+        if not last:
+            for r in range(1, U):
+                z = stepper.jump(z, s, t, draw())
+                z = stepper(z, t, s, 1, k + r * N, draw())
+    return z
+
+
+def sample(net_fn, gamma_fn, z, mode, sampler="dpm2m", steps=None, t_grid=None, eta=0.0, noise_fn=None, known=None,
+           mask=None, known_noise_fn=None, resample=1):
     """z_0 from z_1 = z by `sampler` (ddim | dpm2m | sde2m) over `steps` uniform steps or the explicit `t_grid`; mode as
     ops.fast_sampler_step (0: net_fn gives the velocity, 1: eps_hat, 2: x_hat).  eta (ddim only): 0 is the
-    deterministic sampler; sde2m and ddim with eta > 0 need noise_fn(k) -> xi shaped like z, the noise of step k"""
+    deterministic sampler; sde2m and ddim with eta > 0 need noise_fn(k) -> xi shaped like z, the noise of step k.
+    known, mask (shaped like z: the image as ops.encode_u8 gives it, one byte per element, non-zero = keep): inpainting
+    with `resample` passes per step, on known_noise_fn(j) -> xi shaped like z (run_inpaint states which j is drawn
+    when)"""
     step_eta = check_eta(sampler, eta)
+    check_inpaint(sampler, known, mask, resample)
     grid = time_grid(steps, t_grid)
     orders = step_orders(sampler, len(grid) - 1)
     with torch.no_grad():
-        return run(EagerStepper(net_fn, gamma_fn, mode, step_eta, noise_fn), z, grid, orders)
+        return run(EagerStepper(net_fn, gamma_fn, mode, step_eta, noise_fn, known, mask, known_noise_fn), z, grid,
+                   orders, resample)

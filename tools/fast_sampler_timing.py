@@ -1,12 +1,14 @@
 """Wall time per batch of the samplers on one MI355X at the full CIFAR-10 configuration (random-init weights: the time
 does not depend on them).  Forms, alternated within one run after one untimed warm-up pass of each:
   ancestral T = 1000 (replayed reverse step), ddim N = 50 (replayed), dpm2m N = 25 replayed, dpm2m N = 25 eager,
-  sde2m N = 25 replayed (the stochastic step: one randn and one more read of the latent's size per step).
+  sde2m N = 25 replayed (the stochastic step: one randn and one more read of the latent's size per step);
+  with --inpaint also dpm2m N = 25 replayed under a half:left mask at resample 1 (25 network evaluations, one mix per
+  step) and at resample 2 (49 evaluations, a jump and a mix more per repeated step).
 Each time is one batch from z_1 to the uint8 images (the loop plus generate_x) with the stepper built beforehand (what
 `python -m ldm.sample` pays per batch), between two device synchronisations.  One JSON line per timed batch, then a
 summary line (median ms per batch).
 
-    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3] [--few-step-only]
+    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3] [--few-step-only] [--inpaint]
 """
 import argparse
 import json
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--few-step-only", action="store_true", help="leave the 1000-step ancestral form out")
+    ap.add_argument("--inpaint", action="store_true", help="add dpm2m with a mask at resample 1 and 2")
     args = ap.parse_args()
     import torch
     from mulan_amd.config import load_config_file
@@ -64,6 +67,19 @@ def main():
     forms = [("ancestral_T1000_replayed", run_ancestral), ("ddim_N50_replayed", fast("ddim", 50, fast_replay)),
              ("dpm2m_N25_replayed", fast("dpm2m", 25, fast_replay)), ("dpm2m_N25_eager", fast("dpm2m", 25, fast_eager)),
              ("sde2m_N25_replayed", fast("sde2m", 25, sde_replay, rng.fold_in(1)))]
+    if args.inpaint:
+        from mulan_amd import ops, sampling
+        with torch.no_grad():
+            mask_replay = model.fast_stepper(params, B, dev, ctx, graph=True, inpaint=True)
+        assert type(mask_replay).__name__ == "GraphedFastStep"
+        known = ops.encode_u8(torch.randint(0, 256, (B, 3072), dtype=torch.uint8, device=dev))
+        mask = sampling.expand_mask(sampling.mask_from_spec("half:left"), B, dev)
+
+        def inpaint(U):
+            return lambda: model.generate_x(params, model.fast_sample(
+                params, z1, ctx, "dpm2m", 25, stepper=mask_replay, known=known, mask=mask, resample=U,
+                known_noise=rng.fold_in(2)), ctx["coeffs"])
+        forms += [("dpm2m_N25_inpaint_resample1_replayed", inpaint(1)), ("dpm2m_N25_inpaint_resample2_replayed", inpaint(2))]
     if args.few_step_only:
         forms = forms[1:]
     times = {name: [] for name, _ in forms}
