@@ -500,6 +500,28 @@ int mulan_inpaint_mix(const float* z, const float* x, const unsigned char* mask,
  * mulan_inpaint_mix; xi is required. */
 int mulan_forward_jump(const float* zs, const float* gs, const float* gt, const float* xi, float* zt, size_t n,
                        int g_per_sample, mulan_stream_t stream);
+/* Restoration with the few-step samplers (not in the reference): the projection of a data prediction onto a linear
+ * measurement whose pseudo-inverse is replication (DDNM).  A degradation (f, gray) partitions the H x W x C sub-pixels
+ * of an image (HWC) into equal groups and A takes each group's mean:
+ *   gray = 0, f in {2, 4, 8, 16}: f x f average pooling per channel, group (h / f, w / f, c), y [B, H/f, W/f, C];
+ *   gray = 1, f = 1: the channel mean, group (h, w), y [B, H, W, 1];
+ *   gray = 1, f in {2, 4, 8, 16}: both, group (h / f, w / f), y [B, H/f, W/f, 1].
+ * mulan_restore_project forms x_hat from (z, net, g_t) with the expressions of mulan_fast_sampler_step (mode 0 / 1 / 2;
+ * the bits of that kernel's x0 output) and writes, per element i of group g,
+ *   xh_out[i] = x_hat[i] + (y[g] - mean_{j in g} x_hat[j]).
+ * gamma per element (g_per_sample = 0) or per sample (g_per_sample = H W C: g_t [B]).  xh_out may be z or net.
+ * One launch, one block per row band of f image rows, the band held in LDS; a group's mean is an fp32 sum in an order
+ * that (f, gray, C) fix, divided by the group size: no atomics, the same bits on every run.
+ * hipErrorInvalidValue for a NULL pointer, mode outside 0..2, B H W C == 0 (or a negative extent), an f outside the list
+ * (f = 1 without gray included) or one that does not divide H and W, a g_per_sample that is neither 0 nor H W C, a band
+ * beyond LDS (f W C + groups per band > 16384 floats), more than 2^24 - 1 bands (B H / f; a launch holds fewer than 2^32
+ * threads). */
+int mulan_restore_project(const float* z, const float* net, const float* g_t, const float* y, float* xh_out, int B, int H,
+                          int W, int C, int f, int gray, int mode, int g_per_sample, mulan_stream_t stream);
+/* y_out = A x for the degradation (f, gray) of mulan_restore_project, by the same reduction in the same order: projecting
+ * x (mode 2) onto mulan_restore_measure(x) returns x bit for bit.  Refusals as mulan_restore_project. */
+int mulan_restore_measure(const float* x, float* y_out, int B, int H, int W, int C, int f, int gray,
+                          mulan_stream_t stream);
 /* out[r] = mean(x[r, :])  (VDM._get_score_model_gt, model_mulan_velocity.py:141-146) */
 int mulan_rowmean(const float* x, float* out, int rows, int cols, mulan_stream_t stream);
 

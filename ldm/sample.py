@@ -2,6 +2,7 @@
                       [--sampler dpm2m|sde2m|ddim|ancestral] [--eta 0.0] [--steps 25] [--batch_size B]
                       [--embedding deterministic|random] [--seed 0]
                       [--inpaint_images=FILE.npz [--mask box:y0,x0,y1,x1|half:left|right|top|bottom] [--resample 1]]
+                      [--restore_images=FILE.npz [--degradation sr:4|gray|sr:4+gray] [--resample 1]]
 
 Writes a set of samples of a checkpoint's EMA parameters (Experiment_Colab) to one .npz: `images` (uint8
 [n_samples, 32, 32, 3]) and the run's settings.  Not in the reference, which writes image grids only.  Global batch b
@@ -15,7 +16,16 @@ non-zero = keep) inpaints instead: image b B + j goes to slot j of global batch 
 in and the rest is sampled (Experiment_Colab.sample_batches with known / mask; the known region's noise comes from a
 fourth sub-key of the batch's key).  --mask names the mask where the file has none; --resample=U runs U passes per step;
 --n_samples defaults to N; --embedding also takes `encoder`.  The output then holds `mask` (uint8 [n_samples, 32, 32])
-too."""
+too.
+
+--restore_images=FILE.npz restores instead: the file holds either `images` (uint8 [N, 32, 32, 3]), which the run degrades
+by --degradation (sr:f: f x f average pooling, f in 2, 4, 8, 16; gray: the channel mean; sr:f+gray: both; default sr:4),
+or their `measurement` ([N, 32 / f, 32 / f, 3 or 1 with gray], uint8 levels or fp32 in the model's [-1, 1] scale).  Every
+step's prediction is projected onto the measurement (Experiment_Colab.sample_batches with measurement / degradation);
+--resample=U runs U passes per step, the jumps drawn from the fourth sub-key.  Slots, --n_samples and --embedding as with
+--inpaint_images, which it excludes, as it does the ancestral sampler.  The output then holds `measurement` (fp32
+[n_samples, ...], the scale above), `degradation` and `residual` (fp32 [n_samples]: the largest |A encode(image) - y|
+per image in grey levels)."""
 import io
 import json
 import logging
@@ -23,6 +33,7 @@ import math
 import os
 import sys
 import zipfile
+from collections import namedtuple
 
 import numpy as np
 
@@ -47,7 +58,9 @@ def make_flags():
     flags.DEFINE_integer('seed', 0, 'Global batch b is drawn from PRNGKey(seed).fold_in(b).')
     flags.DEFINE_string('inpaint_images', None, 'Inpaint the images of this .npz (images, optionally mask).')
     flags.DEFINE_string('mask', None, 'box:y0,x0,y1,x1 (unknown box) / half:left|right|top|bottom (kept half).')
-    flags.DEFINE_integer('resample', 1, 'Inpainting: passes per step (1: no resampling).')
+    flags.DEFINE_integer('resample', 1, 'Inpainting and restoration: passes per step (1: no resampling).')
+    flags.DEFINE_string('restore_images', None, 'Restore from this .npz (images to degrade, or their measurement).')
+    flags.DEFINE_string('degradation', None, 'sr:f (f in 2, 4, 8, 16) / gray / sr:f+gray; default sr:4.')
     flags.DEFINE_string('out', None, 'Output file (.npz).')
     flags.DEFINE_string('log_level', 'info', 'info/warning/error')
     flags.mark_flags_as_required(['config', 'checkpoint_directory', 'out'])
@@ -61,9 +74,11 @@ def inpaint_inputs(flags):
     if flags.inpaint_images is None:
         if flags.mask is not None:
             raise SystemExit("--mask names the mask of --inpaint_images; there are no images")
-        if flags.resample != 1:
-            raise SystemExit("--resample applies to --inpaint_images")
+        if flags.resample != 1 and flags.restore_images is None:
+            raise SystemExit("--resample applies to --inpaint_images and --restore_images")
         return None
+    if flags.restore_images is not None:
+        raise SystemExit("--inpaint_images and --restore_images exclude each other: inpaint or restore")
     if flags.sampler == 'ancestral':
         raise SystemExit("--inpaint_images runs with --sampler=ddim, dpm2m or sde2m; the ancestral sampler takes no mask")
     if flags.resample < 1:
@@ -95,13 +110,54 @@ def inpaint_inputs(flags):
     return images, np.ascontiguousarray(np.broadcast_to(mask != 0, (N, 32, 32)))
 
 
+# what --restore_images / --degradation name: `array` is the file's `images` (uint8 [N, 32, 32, 3], degrade True: the run
+# degrades them) or its `measurement` ([N, 32 / f, 32 / f, 3 or 1], uint8 or float32, degrade False); (f, gray) is `spec` parsed
+RestoreInputs = namedtuple("RestoreInputs", "array degrade f gray spec")
+
+
+def restore_inputs(flags):
+    """-> RestoreInputs named by --restore_images / --degradation, None without --restore_images, or SystemExit"""
+    from mulan_amd.sampling import parse_degradation
+    if flags.restore_images is None:
+        if flags.degradation is not None:
+            raise SystemExit("--degradation names what --restore_images went through; there are no images")
+        return None
+    if flags.sampler == 'ancestral':
+        raise SystemExit("--restore_images runs with --sampler=ddim, dpm2m or sde2m; the ancestral sampler takes no "
+                         "measurement")
+    if flags.resample < 1:
+        raise SystemExit(f"--resample must be >= 1, got {flags.resample}")
+    spec = flags.degradation if flags.degradation is not None else 'sr:4'
+    try:
+        f, gray = parse_degradation(spec)
+    except ValueError as e:
+        raise SystemExit(f"--degradation: {e}") from None
+    try:
+        with np.load(flags.restore_images, allow_pickle=False) as z:
+            images = z['images'] if 'images' in z.files else None
+            y = z['measurement'] if 'measurement' in z.files else None
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--restore_images: cannot read {flags.restore_images!r} ({e})") from None
+    if (images is None) == (y is None):
+        raise SystemExit("--restore_images: the file needs `images` (to degrade) or `measurement`, one of the two")
+    if images is not None and (images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (32, 32, 3)
+                               or not len(images)):
+        raise SystemExit("--restore_images: `images` is uint8 [N, 32, 32, 3] with N >= 1")
+    shape = (32 // f, 32 // f, 1 if gray else 3)
+    if y is not None and (y.dtype not in (np.uint8, np.float32) or y.ndim != 4 or y.shape[1:] != shape or not len(y)):
+        raise SystemExit(f"--restore_images: the `measurement` of {spec} is uint8 or float32 [N, {shape[0]}, {shape[1]}, "
+                         f"{shape[2]}] with N >= 1, got {y.dtype} {list(y.shape)}")
+    return RestoreInputs(images if y is None else y, y is None, f, gray, spec)
+
+
 def parse_flags(argv):
     """-> (flags, batch_size) or SystemExit: every check that needs no device"""
     return parse_all(argv)[:2]
 
 
 def parse_all(argv):
-    """-> (flags, batch_size, inpaint_inputs(flags)): parse_flags with the images and masks it read on the way"""
+    """-> (flags, batch_size, inpaint_inputs(flags), restore_inputs(flags), given): parse_flags with the arrays it read
+    on the way; given: the array with one entry per image to produce (None: an unconditional run)"""
     flags = make_flags().parse(argv)
     if flags.sampler not in SAMPLERS:
         raise SystemExit(f"unknown --sampler {flags.sampler!r} (one of {', '.join(SAMPLERS)})")
@@ -110,17 +166,20 @@ def parse_all(argv):
     if flags.eta != 0.0 and flags.sampler != 'ddim':
         raise SystemExit(f"--eta applies to --sampler=ddim; {flags.sampler!r} takes none")
     inpaint = inpaint_inputs(flags)
-    embeddings = EMBEDDINGS + (('encoder',) if inpaint else ())
+    restore = restore_inputs(flags)
+    given = inpaint[0] if inpaint else restore.array if restore else None     # the input images, or their measurements
+    embeddings = EMBEDDINGS + (('encoder',) if given is not None else ())
     if flags.embedding not in embeddings:
         raise SystemExit(f"unknown --embedding {flags.embedding!r} (one of {', '.join(embeddings)})")
     if flags.steps < 1:
         raise SystemExit(f"--steps must be >= 1, got {flags.steps}")
-    if flags.n_samples is None and inpaint is None:
+    if flags.n_samples is None and given is None:
         raise SystemExit("flag --n_samples is required")
     if flags.n_samples is not None and flags.n_samples < 1:
         raise SystemExit(f"--n_samples must be >= 1, got {flags.n_samples}")
-    if inpaint is not None and flags.n_samples is not None and flags.n_samples > len(inpaint[0]):
-        raise SystemExit(f"--n_samples={flags.n_samples}, but --inpaint_images holds {len(inpaint[0])} images")
+    if given is not None and flags.n_samples is not None and flags.n_samples > len(given):
+        raise SystemExit(f"--n_samples={flags.n_samples}, but --{'inpaint' if inpaint else 'restore'}_images holds "
+                         f"{len(given)} images")
     batch_size = flags.batch_size if flags.batch_size is not None else int(flags.config.training.batch_size_eval)
     if batch_size < 1:
         raise SystemExit(f"--batch_size must be >= 1, got {batch_size}")
@@ -130,7 +189,7 @@ def parse_all(argv):
         raise SystemExit(f"--embedding={flags.embedding} needs a MuLAN model (vdm_type mulan_velocity / mulan_epsilon)")
     if not ckpt_lib.checkpoint_numbers(flags.checkpoint_directory):
         raise SystemExit(f'no ckpt-* files in {flags.checkpoint_directory}')
-    return flags, batch_size, inpaint
+    return flags, batch_size, inpaint, restore, given
 
 
 def write_npz(path, arrays):
@@ -145,7 +204,7 @@ def write_npz(path, arrays):
 
 
 def main(argv):
-    flags, batch_size, inpaint = parse_all(argv)
+    flags, batch_size, inpaint, restore, given = parse_all(argv)
     rank = int(os.environ.get("RANK", "0"))
     logging.basicConfig(level=getattr(logging, flags.log_level.upper()) if rank == 0 else logging.ERROR)
     import torch
@@ -156,7 +215,7 @@ def main(argv):
     ckpt_num = ckpt_nums[-1] if flags.checkpoint is None else flags.checkpoint
     experiment = Experiment_Colab(flags.config, flags.checkpoint_directory, ckpt_num)
     world, rank = experiment.world, experiment.rank
-    n_samples = flags.n_samples if flags.n_samples is not None else len(inpaint[0])
+    n_samples = flags.n_samples if flags.n_samples is not None else len(given)
     n_batches = math.ceil(n_samples / batch_size)
     mine = list(range(rank, n_batches, world))
     per_rank = math.ceil(n_batches / world)
@@ -170,6 +229,18 @@ def main(argv):
         known[:n_samples], keep[:n_samples] = inpaint[0][:n_samples], inpaint[1][:n_samples]
         rows = lambda a, b: torch.from_numpy(a[b * batch_size:(b + 1) * batch_size])
         kw = dict(known=[rows(known, b) for b in mine], mask=[rows(keep, b) for b in mine], resample=flags.resample)
+    if restore is not None:
+        # as above; the slots past the last image hold the measurement of a black image.  Every rank forms the whole
+        # measurement (it is small), so the file does not depend on the number of ranks
+        from mulan_amd import ops
+        pad = n_batches * batch_size
+        src = np.zeros((pad,) + given.shape[1:], dtype=given.dtype)
+        src[:n_samples] = given[:n_samples]
+        src = torch.from_numpy(src).to(experiment.device)
+        enc = ops.encode_u8(src) if src.dtype == torch.uint8 else src
+        y_all = ops.restore_measure(enc, restore.f, restore.gray) if restore.degrade else enc
+        kw = dict(measurement=[y_all[b * batch_size:(b + 1) * batch_size].contiguous() for b in mine],
+                  degradation=restore.spec, resample=flags.resample)
     images = experiment.sample_batches([root.fold_in(b) for b in mine], batch_size, flags.embedding, flags.sampler,
                                        flags.steps, flags.eta, **kw)
     local = torch.zeros((per_rank, batch_size, 32, 32, 3), dtype=torch.uint8, device=experiment.device)
@@ -186,6 +257,14 @@ def main(argv):
         if inpaint is not None:
             settings.update(inpaint=True, resample=flags.resample, mask=flags.mask)
             arrays['mask'] = inpaint[1][:n_samples].astype(np.uint8)
+        if restore is not None:
+            settings.update(restore=True, resample=flags.resample, degradation=restore.spec)
+            y = y_all[:n_samples]
+            back = ops.restore_measure(ops.encode_u8(torch.from_numpy(out).to(experiment.device)), restore.f,
+                                        restore.gray)
+            residual = (back - y).abs().reshape(n_samples, -1).amax(dim=1) * 127.5
+            arrays.update(measurement=y.cpu().numpy(), degradation=np.array(restore.spec),
+                          residual=residual.cpu().numpy())
         write_npz(flags.out, dict(arrays, settings=np.array(json.dumps(settings, sort_keys=True))))
         print(f'wrote {out.shape[0]} samples ({flags.sampler}, {flags.steps} steps) to {flags.out}')
     return 0

@@ -96,7 +96,7 @@ class Experiment_Colab(Experiment_VDM):
             raise ValueError("embedding='encoder' takes the hard top-k of the encoder's logits; latent_type 'gaussian' "
                              "has none")
 
-    def _batch_embedding(self, embedding, k_e, batch_size, known=None, mask=None):
+    def _batch_embedding(self, embedding, k_e, batch_size, known=None, mask=None, measurement=None, restore=None):
         """the [B, 50] embedding of one batch (None: draw_samples takes the model's deterministic one)"""
         from . import ops
         if not isinstance(embedding, str):
@@ -104,6 +104,13 @@ class Experiment_Colab(Experiment_VDM):
             return emb.reshape(-1, 50).expand(batch_size, 50).contiguous()
         if embedding == 'random':
             return ops.topk_hard(k_e.normal((batch_size, 50), self.device), 15)[0]
+        if embedding == 'encoder' and restore is not None:
+            # the encoder sees A+ y: every group's measured value at all of its sub-pixels, as 8-bit levels
+            f, gray = restore
+            y = torch.as_tensor(measurement).to(self.device)
+            up = y.repeat_interleave(f, 1).repeat_interleave(f, 2).expand(batch_size, 32, 32, 3)
+            levels = ((up + 1.0) * 128.0 - 0.5).round().clamp(0, 255).to(torch.uint8).contiguous()   # encode_u8 inverted
+            return ops.topk_hard(self.model.apply_encoder(self.params, levels), self.model.config.latent_k)[0]
         if embedding == 'encoder':
             keep = sampling.expand_mask(mask, batch_size, self.device).view(batch_size, 32, 32, 3) != 0
             known = torch.as_tensor(known).to(self.device)
@@ -112,7 +119,7 @@ class Experiment_Colab(Experiment_VDM):
         return None
 
     def sample_batches(self, keys, batch_size, embedding='deterministic', sampler='dpm2m', steps=25, eta=0.0, known=None,
-                       mask=None, resample=1):
+                       mask=None, resample=1, measurement=None, degradation=None):
         """uint8 [batch_size, 32, 32, 3] per key, each batch drawn from its key alone (the python -m ldm.sample CLI):
         key.split(3) -> (prior z_1 ~ sigma_prior N(0, I), random embedding logits, per-step noise); generate_x with
         key.fold_in(steps).  The per-step noise of the ancestral sampler, of sde2m and of ddim with eta > 0 comes from
@@ -125,23 +132,36 @@ class Experiment_Colab(Experiment_VDM):
         the jumps comes from a fourth sub-key, key.fold_in(KNOWN_NOISE_FOLD), folded with the draw's own counter
         (sampling.run_inpaint); the three sub-keys above and their draws are as without a mask.  Inpainting also takes
         embedding 'encoder' (the hard top-k of apply_encoder on the images with the unknown pixels set to 128) or an
-        explicit k-hot tensor [50] or [batch_size, 50]."""
+        explicit k-hot tensor [50] or [batch_size, 50].
+        measurement (one per key: fp32 in the scale of ops.encode_u8, shaped ops.restore_y_shape) and degradation
+        ('sr:f', 'gray' or 'sr:f+gray', one for all): restoration instead (draw_samples), `resample` passes per step.
+        The jumps of resample > 1 draw from the same fourth sub-key; resample = 1 draws nothing from it.  The embeddings
+        of inpainting apply, 'encoder' on the replicated measurement A+ y rounded to 8-bit levels."""
         sampling.check_eta(sampler, eta)
         keys = list(keys)
-        inpaint = sampling.check_inpaint(sampler, known, mask, resample)
+        restore = sampling.check_restore(sampler, measurement, degradation, resample, known, mask)
+        inpaint = sampling.check_inpaint(sampler, known, mask, 1 if restore else resample)
+        if restore:
+            restore = sampling.parse_degradation(degradation)
+            if torch.is_tensor(measurement) or isinstance(measurement, np.ndarray) or len(measurement) != len(keys):
+                raise ValueError(f"{len(keys)} keys need a list of {len(keys)} measurements, one per batch")
         if inpaint:
             if torch.is_tensor(mask) or isinstance(mask, np.ndarray):
                 mask = [mask] * len(keys)
             if len(known) != len(keys) or len(mask) != len(keys):
                 raise ValueError(f"{len(keys)} keys, but {len(known)} batches of known images and {len(mask)} masks")
-        self._check_embedding(embedding, batch_size, inpaint)
+        self._check_embedding(embedding, batch_size, inpaint or bool(restore))
         out, stepper = [], None
         for b, key in enumerate(keys):
             k_z, k_e, k_s = key.split(3)
             kw = {}
             if inpaint:
                 kw = dict(known=known[b], mask=mask[b], resample=resample, known_rng=key.fold_in(self.KNOWN_NOISE_FOLD))
-            emb = self._batch_embedding(embedding, k_e, batch_size, kw.get("known"), kw.get("mask"))
+            if restore:
+                kw = dict(measurement=measurement[b], degradation=degradation, resample=resample,
+                          known_rng=key.fold_in(self.KNOWN_NOISE_FOLD))
+            emb = self._batch_embedding(embedding, k_e, batch_size, kw.get("known"), kw.get("mask"),
+                                        kw.get("measurement"), restore or None)
             x, stepper = self.draw_samples(self.params, batch_size, emb, k_z, k_s, key.fold_in(steps), sampler, steps,
                                            prior_scale=float(self.config.model.sigma_prior), stepper=stepper, eta=eta,
                                            **kw)
@@ -163,6 +183,42 @@ class Experiment_Colab(Experiment_VDM):
         key = (self.rng if rng is None else rng).fold_in(self.rank)
         return self.sample_batches([key], images.shape[0], embedding, sampler, steps, eta, known=[images], mask=[mask],
                                    resample=resample)[0]
+
+    def restore(self, images=None, measurement=None, degradation='sr:4', embedding='deterministic', sampler='sde2m',
+                steps=25, eta=0.0, resample=1, rng=None):
+        """(restored uint8 [B, 32, 32, 3], residual fp32 [B]): images consistent with a degraded observation, drawn by a
+        few-step sampler whose every prediction is projected onto the measurement (sampling.run_restore).
+        degradation: 'sr:f' (the f x f average-pooled image, f in 2, 4, 8, 16), 'gray' (the channel mean) or 'sr:f+gray'.
+        Exactly one of: images (uint8 [B, 32, 32, 3]), which are degraded here (ops.restore_measure on their encoding),
+        or measurement ([B, 32 / f, 32 / f, 3 or 1 with gray]; fp32 in the scale of ops.encode_u8, or uint8 levels, which
+        are encoded like an image).  residual: the largest |A encode(restored) - y| of each image in grey levels
+        (x 127.5): what per-pixel schedules inside a group and the 8-bit decoding leave of A x = y; reported, not
+        asserted.  resample = U > 1: U passes per step.  embedding as inpaint takes it, 'encoder' on the replicated
+        measurement.  rng as inpaint."""
+        from . import ops
+        f, gray = sampling.parse_degradation(degradation)
+        if (images is None) == (measurement is None):
+            raise ValueError("restore takes the images to degrade or their measurement, one of the two")
+        if images is not None:
+            images = torch.as_tensor(images)
+            if images.dtype != torch.uint8 or images.dim() != 4 or tuple(images.shape[1:]) != (32, 32, 3):
+                raise ValueError(f"images are uint8 [B, 32, 32, 3], got {images.dtype} {list(images.shape)}")
+            B = images.shape[0]
+            y = ops.restore_measure(ops.encode_u8(images.to(self.device)), f, gray)
+        else:
+            y = torch.as_tensor(measurement)
+            B = y.shape[0] if y.dim() == 4 else 0
+            if B < 1 or tuple(y.shape) != ops.restore_y_shape(B, 32, 32, 3, f, gray) or \
+                    y.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"the measurement of {degradation!r} is uint8 or fp32 "
+                                 f"{['B', *ops.restore_y_shape(1, 32, 32, 3, f, gray)[1:]]}, got {y.dtype} {list(y.shape)}")
+            y = y.to(self.device)
+            y = ops.encode_u8(y) if y.dtype == torch.uint8 else y.contiguous()
+        key = (self.rng if rng is None else rng).fold_in(self.rank)
+        out = self.sample_batches([key], B, embedding, sampler, steps, eta, resample=resample, measurement=[y],
+                                  degradation=degradation)[0]
+        back = ops.restore_measure(ops.encode_u8(out), f, gray)
+        return out, (back - y).abs().reshape(B, -1).amax(dim=1) * 127.5
 
     def test(self, loader):
         """Experiment_Colab.test: mean of the eval scalars over a loader"""

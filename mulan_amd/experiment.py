@@ -595,7 +595,8 @@ class Experiment_VDM(Experiment):
         return None
 
     def draw_samples(self, params, B, embedding, prior_rng, step_rng, decode_rng, sampler, steps, t_grid=None,
-                     prior_scale=1.0, stepper=None, eta=0.0, known=None, mask=None, resample=1, known_rng=None):
+                     prior_scale=1.0, stepper=None, eta=0.0, known=None, mask=None, resample=1, known_rng=None,
+                     measurement=None, degradation=None):
         """One batch of B images, the loop every sampling entry point runs: z_1 = prior_scale * N(0, I) from prior_rng,
         `steps` steps of `sampler` under `embedding` (MuLAN models; None: model.deterministic_embedding) with the per-step
         noise of the ancestral sampler from step_rng (rng.fold_in(i) at step i), generate_x with decode_rng (needed by
@@ -608,9 +609,21 @@ class Experiment_VDM(Experiment):
         passes per step.  The noise of the known region and of the jumps comes from known_rng alone, a key that neither
         z_1 nor the step noise uses: draw j under known_rng.fold_in(j).  With argmax decoding the kept sub-pixels of
         the result are the input's, with no paste-over.
+        measurement (fp32, in the scale of ops.encode_u8, shaped ops.restore_y_shape(B, 32, 32, 3, f, gray)) and
+        degradation ('sr:f', 'gray', 'sr:f+gray'): restoration with the few-step samplers instead (sampling.run_restore):
+        every step's prediction is projected onto the measurement.  resample > 1 draws jump j under known_rng.fold_in(j);
+        resample = 1 draws nothing from known_rng and needs none.  A mask and a measurement in one run are refused.
         -> (uint8 [B, 32, 32, 3], stepper or None)"""
         step_eta = sampling.check_eta(sampler, eta)          # what the steps run with: 1 for sde2m
-        inpaint = sampling.check_inpaint(sampler, known, mask, resample)
+        restore = sampling.check_restore(sampler, measurement, degradation, resample, known, mask)
+        inpaint = sampling.check_inpaint(sampler, known, mask, 1 if restore else resample)
+        if restore:
+            restore = sampling.parse_degradation(degradation)
+            if sampling.check_resample(resample) > 1 and known_rng is None:
+                raise ValueError("draw_samples: resample > 1 needs known_rng, the key of the jumps' noise")
+            measurement = torch.as_tensor(measurement)
+            if measurement.dtype != torch.float32:
+                raise ValueError(f"draw_samples: the measurement is fp32 in the encoded scale, got {measurement.dtype}")
         if inpaint:
             if known_rng is None:
                 raise ValueError("draw_samples: inpainting needs known_rng, the key of the known region's noise")
@@ -645,8 +658,11 @@ class Experiment_VDM(Experiment):
                     ctx = self.model.fast_context(params, embedding if mulan else None, conditioning)
                     if stepper is None:
                         stepper = self.model.fast_stepper(params, B, self.device, ctx, step_eta=step_eta,
-                                                          inpaint=inpaint)
+                                                          inpaint=inpaint, restore=restore or None)
                     kw = {}
+                    if restore:
+                        kw = dict(measurement=measurement.to(self.device), degradation=restore, resample=resample,
+                                  known_noise=known_rng)
                     if inpaint:
                         from . import ops
                         kw = dict(known=ops.encode_u8(known.to(self.device)).reshape(B, 3072), mask=mask,

@@ -118,6 +118,8 @@ SIGNATURES = {
     "mulan_stochastic_sampler_step": [P, P, P, P, P, P, P, F, P, P, Z, I, I, P],
     "mulan_inpaint_mix": [P, P, P, P, P, P, Z, I, P],
     "mulan_forward_jump": [P, P, P, P, P, Z, I, P],
+    "mulan_restore_project": [P, P, P, P, P, I, I, I, I, I, I, I, I, P],
+    "mulan_restore_measure": [P, P, I, I, I, I, I, I, P],
     "mulan_rowmean": [P, P, I, I, P],
     "mulan_ode_drift": [P, P, P, P, P, P, P, Z, I, I, P],
     "mulan_ode_div": [P, P, P, P, P, I, I, I, I, P],

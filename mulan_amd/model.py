@@ -29,6 +29,7 @@ from .rng import Key
 
 HW = 1024
 D = 3072
+HWC = (32, 32, 3)           # an image of D sub-pixels, in the order the samplers' [B, D] states hold it
 
 
 # ----------------------------------------------------------------------------- config / output
@@ -290,25 +291,50 @@ class _KnownBuffers:
         if (mix is not None) != self.inpaint:
             raise ValueError("a stepper built with a mask mixes after every step, and one built without never does")
 
+    # a restoring stepper (sampling.run_restore) keeps the measurement y of its degradation (f, gray) in a static buffer
+    # shaped ops.restore_y_shape, set per batch, and draws the noise of its jumps from the key set_measurement() names
+    def _init_measurement(self, B, device, restore):
+        from . import sampling
+        self.restore = None if restore is None else sampling.parse_degradation(restore)
+        self.y = None
+        if self.restore is not None:
+            if self.inpaint:
+                raise ValueError("a mask and a measurement in one run are not supported: inpaint or restore")
+            self.y = torch.zeros(ops.restore_y_shape(B, *HWC, *self.restore), device=device, dtype=torch.float32)
+
+    def set_measurement(self, y, noise=None):
+        """this batch's measurement (fp32, ops.restore_y_shape values) and the key (or callable j -> xi) of its jumps"""
+        if self.restore is None:
+            raise ValueError("this stepper was built without a degradation (fast_stepper(..., restore=(f, gray)) builds "
+                             "one with)")
+        if y.dtype != torch.float32 or y.numel() != self.y.numel():
+            raise ValueError(f"the measurement is fp32 {list(self.y.shape)}, got {y.dtype} {list(y.shape)}")
+        self.y.copy_(y.reshape(self.y.shape))
+        self.known_noise = noise
+
 
 class EagerFastStep(_KnownBuffers):
     """The eager form of GraphedFastStep (MULAN_SAMPLER_GRAPH=0, or a failed capture): sampling.EagerStepper over the
     model's network and schedule, reading the context through this object so that set_context() re-targets it at the
     next batch like the replayed stepper.  step_eta > 0 (sampling.check_eta): the stochastic step on the noise
-    set_noise() names.  inpaint: the stepper of an inpainting run (sampling.run_inpaint) on what set_known() holds."""
+    set_noise() names.  inpaint: the stepper of an inpainting run (sampling.run_inpaint) on what set_known() holds.
+    restore = (f, gray): the stepper of a restoring run (sampling.run_restore) on what set_measurement() holds."""
 
-    def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False):
+    def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False, restore=None):
         from . import sampling
         self.ctx, self.step_eta, self.noise = ctx, float(step_eta), None
         self._init_known(B, device, inpaint)
+        self._init_measurement(B, device, restore)
+        if self.restore is not None:
+            self.kxi = torch.zeros((B, D), device=device, dtype=torch.float32)      # the noise of a jump
         times = lambda t: torch.full((B,), float(np.float32(t)), device=device, dtype=torch.float32)
         gamma_fn = lambda t: model._fast_gamma(params, self.ctx, times(t))
         net_fn = lambda z, t: model._fast_net(params, z.reshape(B, D), gamma_fn(t), self.ctx).view(z.shape)
         self.xi = torch.zeros((B, D), device=device, dtype=torch.float32) if self.step_eta > 0.0 else None
         noise_fn = (lambda k: _fill_step_noise(self.xi, self.noise, k)) if self.step_eta > 0.0 else None
-        known_fn = (lambda j: _fill_known_noise(self.kxi, self.known_noise, j)) if self.inpaint else None
+        known_fn = (lambda j: _fill_known_noise(self.kxi, self.known_noise, j)) if self.kxi is not None else None
         self._make = lambda: sampling.EagerStepper(net_fn, gamma_fn, model._fast_mode(), self.step_eta, noise_fn,
-                                                   self.known, self.mask, known_fn)
+                                                   self.known, self.mask, known_fn, self.y, self.restore, HWC)
         self._step = self._make()
 
     def set_context(self, ctx):
@@ -347,14 +373,19 @@ class GraphedFastStep(_KnownBuffers):
     inpaint captures the mix behind the step kernel (mulan_inpaint_mix at gamma_s): the known image, the mask and the
     known region's noise are static buffers, the first two set per batch (set_known), the noise filled before each
     replay (_fill_known_noise; zeros for the last step, which the kernel reads as it reads a NULL xi).  The mix of z_1
-    and the jumps of the resampling are eager launches between replays, the jump on a static noise buffer of its own."""
+    and the jumps of the resampling are eager launches between replays, the jump on a static noise buffer of its own.
+    restore = (f, gray) captures the projection (mulan_restore_project) between the network and the step kernel, which
+    then runs at mode 2 on x_hat'; the measurement is a static buffer set per batch (set_measurement), and the history
+    copied after each replay is x_hat'.  The jumps are eager launches as above."""
 
-    def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False):
+    def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False, restore=None):
         self.B, self.step_eta, self.noise = B, float(step_eta), None
         self.model, self.params = model, params
         self._init_known(B, device, inpaint)
+        self._init_measurement(B, device, restore)
         f32 = dict(device=device, dtype=torch.float32)
-        self.jxi = torch.zeros((B, D), **f32) if self.inpaint else None       # the noise of a jump
+        jumps = self.inpaint or self.restore is not None
+        self.jxi = torch.zeros((B, D), **f32) if jumps else None              # the noise of a jump
         self.ctx = {k: (None if v is None else tuple(c.detach().clone() for c in v) if isinstance(v, tuple)
                         else v.detach().clone()) for k, v in ctx.items()}
         self.z_in, self.x_prev = torch.zeros((B, D), **f32), torch.zeros((B, D), **f32)
@@ -362,7 +393,7 @@ class GraphedFastStep(_KnownBuffers):
         self.g_prev = torch.full(model._fast_gamma_shape(B), float("nan"), **f32)
         self.xi = torch.zeros((B, D), **f32) if self.step_eta > 0.0 else None
         run = lambda: model._fast_step(params, self.z_in, self.t, self.s, self.g_prev, self.x_prev, self.ctx, self.xi,
-                                       self.step_eta, self.known, self.mask, self.kxi)
+                                       self.step_eta, self.known, self.mask, self.kxi, self.y, self.restore)
         with torch.no_grad():
             self.graph, (self.z_out, self.x_out, self.g_out) = _capture(run)
         self.has_history = False
@@ -739,37 +770,44 @@ class _VDMBase:
 
     # ---- few-step samplers (mulan_amd.sampling; not in the reference) ----------------------------------------------
     def _fast_step(self, params, z, t, s, g_prev, x_prev, ctx, xi=None, step_eta=0.0, known=None, mask=None,
-                   known_xi=None):
+                   known_xi=None, measurement=None, restore=None):
         """the device work of one step t -> s: (z_s, x_hat_t, gamma_t); g_prev / x_prev None: first order; xi [B, 3072]
         with step_eta > 0: the stochastic step on that noise; known / mask [B, 3072] (inpainting): the known sub-pixels
-        of z_s are then replaced by alpha_s known + sigma_s known_xi (known_xi None: zero noise)"""
+        of z_s are then replaced by alpha_s known + sigma_s known_xi (known_xi None: zero noise); measurement with
+        restore = (f, gray): the prediction is projected onto the measurement and the step runs on x_hat' at mode 2, so
+        the x_hat_t returned is x_hat'"""
         g_t = self._fast_gamma(params, ctx, t)
         g_s = self._fast_gamma(params, ctx, s)
-        net = self._fast_net(params, z, g_t, ctx)
+        net, mode = self._fast_net(params, z, g_t, ctx), self._fast_mode()
+        if restore is not None:
+            net, mode = ops.restore_project(z, net, g_t, measurement, *restore, mode, HWC), 2
         if xi is not None:
-            z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, self._fast_mode(), xi, step_eta, g_prev,
+            z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, mode, xi, step_eta, g_prev,
                                                       x_prev)
         else:
-            z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, self._fast_mode(), g_prev, x_prev)
+            z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, mode, g_prev, x_prev)
         if mask is not None:
             z_s = ops.inpaint_mix(z_s, known, mask, g_s, known_xi, out=z_s)
         return z_s, x0, g_t
 
-    def fast_stepper(self, params, B, device, ctx, graph=None, step_eta=0.0, inpaint=False):
+    def fast_stepper(self, params, B, device, ctx, graph=None, step_eta=0.0, inpaint=False, restore=None):
         """-> step(z, t, s, order[, k]) of the few-step samplers: a replayed HIP graph (GraphedFastStep) by default
         (MULAN_SAMPLER_GRAPH), eager where the capture fails (logged) or graph=False (EagerFastStep); both take the next
         batch's context through set_context().  step_eta > 0 (the eta the steps run with, what sampling.check_eta
         makes of a sampler and its `eta` keyword: 1 for sde2m): the stochastic step, whose noise the
         stepper draws for step k from what set_noise() names.  inpaint: a stepper that replaces the known sub-pixels
         after every step, on the image, mask and known-region noise of set_known(); it serves inpainting runs only,
-        and a stepper built without serves none"""
+        and a stepper built without serves none.  restore = (f, gray) (sampling.parse_degradation): a stepper that
+        projects every prediction onto the measurement of set_measurement(); it serves restoring runs of that
+        degradation only"""
         return _graphed_or_eager(SAMPLER_GRAPH if graph is None else graph, device,
-                                 lambda: GraphedFastStep(self, params, B, device, ctx, step_eta, inpaint),
-                                 lambda: EagerFastStep(self, params, B, device, ctx, step_eta, inpaint),
+                                 lambda: GraphedFastStep(self, params, B, device, ctx, step_eta, inpaint, restore),
+                                 lambda: EagerFastStep(self, params, B, device, ctx, step_eta, inpaint, restore),
                                  "HIP-graph capture of the few-step sampler's step failed (%s: %s); sampling eagerly")
 
     def fast_sample(self, params, z, ctx, sampler="dpm2m", steps=None, t_grid=None, graph=None, stepper=None, eta=0.0,
-                    noise=None, known=None, mask=None, resample=1, known_noise=None):
+                    noise=None, known=None, mask=None, resample=1, known_noise=None, measurement=None,
+                    degradation=None):
         """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m | sde2m) over `steps` uniform steps or the explicit
         t_grid; stepper: one from fast_stepper to re-use (its set_context re-targets it at this batch's ctx).
         eta: for ddim (0: the deterministic sampler).  noise (sde2m, ddim with eta > 0): the batch's step key -- step k
@@ -778,11 +816,26 @@ class _VDMBase:
         inpainting (sampling.run_inpaint) with `resample` passes per step.  known_noise: the batch's known-region key --
         draw j of the run (the noise of the known region at a mix, or of a jump; run_inpaint states which j is drawn
         when) is randn under known_noise.fold_in(j) -- or a callable j -> xi [B, 3072].  It is a key of its own: step k
-        keeps drawing under noise.fold_in(k), and round r of a resampled step k under noise.fold_in(k + r N)"""
+        keeps drawing under noise.fold_in(k), and round r of a resampled step k under noise.fold_in(k + r N).
+        measurement (fp32, shaped ops.restore_y_shape(B, 32, 32, 3, f, gray), in the scale of ops.encode_u8) and
+        degradation ('sr:f', 'gray', 'sr:f+gray' or the pair (f, gray)): restoration instead (sampling.run_restore) with
+        `resample` passes per step; jump j of a run with resample > 1 draws under known_noise.fold_in(j), and a run with
+        resample = 1 needs no known_noise"""
         from . import sampling
         step_eta = sampling.check_eta(sampler, eta)
-        inpaint = sampling.check_inpaint(sampler, known, mask, resample)
+        restoring = sampling.check_restore(sampler, measurement, degradation, resample, known, mask)
+        inpaint = sampling.check_inpaint(sampler, known, mask, 1 if restoring else resample)
         B = z.shape[0]
+        restore = None
+        if restoring:
+            restore = sampling.parse_degradation(degradation)
+            shape = ops.restore_y_shape(B, *HWC, *restore)
+            if not torch.is_tensor(measurement) or measurement.dtype != torch.float32 or tuple(measurement.shape) != shape:
+                got = (f"{measurement.dtype} {list(measurement.shape)}" if torch.is_tensor(measurement)
+                       else type(measurement).__name__)
+                raise ValueError(f"fast_sample: the measurement of {degradation!r} is fp32 {list(shape)}; got {got}")
+            if sampling.check_resample(resample) > 1 and known_noise is None:
+                raise ValueError("fast_sample: resample > 1 needs `known_noise` (the key of the jumps' noise)")
         if inpaint:
             if known.dtype != torch.float32 or tuple(known.shape) != (B, D):
                 raise ValueError(f"fast_sample: known is the encoded image, fp32 [{B}, {D}]; got {known.dtype} "
@@ -797,7 +850,7 @@ class _VDMBase:
             raise ValueError(f"fast_sample: {sampler!r} with eta = {step_eta} is stochastic and needs `noise`")
         with torch.no_grad():
             if stepper is None:
-                stepper = self.fast_stepper(params, B, z.device, ctx, graph, step_eta, inpaint)
+                stepper = self.fast_stepper(params, B, z.device, ctx, graph, step_eta, inpaint, restore)
             elif not hasattr(stepper, "set_context"):
                 raise TypeError("fast_sample: a re-used stepper must take the batch's context (set_context): "
                                 f"{type(stepper).__name__} cannot be re-targeted")
@@ -807,12 +860,18 @@ class _VDMBase:
             elif bool(getattr(stepper, "inpaint", False)) != inpaint:
                 raise ValueError("fast_sample: the stepper was built %s a mask, this run comes %s one"
                                  % (("without", "with") if inpaint else ("with", "without")))
+            elif getattr(stepper, "restore", None) != restore:
+                name = lambda r: "no degradation" if r is None else f"the degradation (f, gray) = {r}"
+                raise ValueError(f"fast_sample: the stepper was built for {name(getattr(stepper, 'restore', None))}, "
+                                 f"this run comes with {name(restore)}")
             else:
                 stepper.set_context(ctx)
             if step_eta > 0.0:
                 stepper.set_noise(noise)
             if inpaint:
                 stepper.set_known(known, mask, known_noise)
+            if restoring:
+                stepper.set_measurement(measurement, known_noise)
             return sampling.run(stepper, z.reshape(B, D).contiguous(), grid, orders, resample)
 
 

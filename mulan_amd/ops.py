@@ -2249,6 +2249,72 @@ def forward_jump(z_s, g_s, g_t, xi):
     return z_t
 
 
+RESTORE_FACTORS = (2, 4, 8, 16)
+
+
+def restore_y_shape(B, H, W, C, f, gray):
+    """shape of the measurement y = A x of the degradation (f, gray) on B images [H, W, C] (mulan_restore_project):
+    f x f average pooling per channel (f in RESTORE_FACTORS; 1: none, with gray only), then the channel mean if gray"""
+    gray = bool(gray)
+    if isinstance(f, bool) or int(f) != f or not (f in RESTORE_FACTORS or (f == 1 and gray)):
+        raise ValueError(f"restore: the factor is one of {RESTORE_FACTORS} (or 1 with gray), got f = {f!r}, gray = {gray}")
+    if min(B, H, W, C) < 1 or H % f or W % f:
+        raise ValueError(f"restore: f = {f} must divide H = {H} and W = {W}, and no extent may be zero (B = {B}, C = {C})")
+    return (B, H // f, W // f, 1 if gray else C)
+
+
+def _restore_dims(x, hwc, name):
+    if hwc is None:
+        if x.dim() != 4:
+            raise ValueError(f"{name}: an input that is not [B, H, W, C] needs hwc = (H, W, C)")
+        return tuple(x.shape)
+    H, W, C = (int(v) for v in hwc)
+    if min(H, W, C) < 1 or x.numel() == 0 or x.numel() % (H * W * C):
+        raise ValueError(f"{name}: {x.numel()} elements are no batch of [{H}, {W}, {C}] images")
+    return (x.numel() // (H * W * C), H, W, C)
+
+
+def restore_measure(x, f, gray, hwc=None):
+    """y = A x (mulan_restore_measure): the group means of the degradation (f, gray), fp32 shaped restore_y_shape.
+    x: fp32 [B, H, W, C], or any shape holding B images with hwc = (H, W, C)"""
+    _chk(x, "restore_measure: x")
+    B, H, W, C = _restore_dims(x, hwc, "restore_measure")
+    y = torch.empty(restore_y_shape(B, H, W, C, f, gray), device=x.device, dtype=torch.float32)
+    call("mulan_restore_measure", ptr(_c(x)), ptr(y), B, H, W, C, int(f), int(bool(gray)), stream())
+    return y
+
+
+def restore_project(z, net, g_t, y, f, gray, mode, hwc=None, out=None):
+    """x_hat' = x_hat + A+ (y - A x_hat) (mulan_restore_project): x_hat formed from (z, net, g_t) as fast_sampler_step
+    forms it for `mode` (0: net is the velocity, 1: eps_hat, 2: x_hat, and z is not used), projected onto the measurement
+    y (fp32, restore_y_shape elements) of the degradation (f, gray).  z: fp32 [B, H, W, C], or any shape holding B images
+    with hwc = (H, W, C); g_t per element or per sample ([B]).  Returns a new tensor shaped like z (out: the tensor to
+    write, which may be z or net)"""
+    for t, name in ((z, "z"), (net, "net"), (g_t, "g_t"), (y, "y")):
+        if not torch.is_tensor(t):
+            raise ValueError(f"restore_project: {name} is a tensor, got {type(t).__name__}")
+        _chk(t, f"restore_project: {name}")
+    if mode not in (0, 1, 2):
+        raise ValueError(f"restore_project: mode is 0 (velocity), 1 (eps_hat) or 2 (x_hat), got {mode!r}")
+    B, H, W, C = _restore_dims(z, hwc, "restore_project")
+    if net.numel() != z.numel():
+        raise ValueError("restore_project: net holds one value per element of z")
+    if g_t.numel() not in (B, z.numel()):
+        raise ValueError("restore_project: gamma is per element or per sample")
+    ys = restore_y_shape(B, H, W, C, f, gray)
+    if y.numel() != math.prod(ys):
+        raise ValueError(f"restore_project: the measurement holds {list(ys)} values, got {list(y.shape)}")
+    z, net, g_t, y = _c(z), _c(net), _c(g_t), _c(y)
+    if out is None:
+        out = torch.empty_like(z)
+    elif out.shape != z.shape or out.dtype != torch.float32 or out.device != z.device or not out.is_contiguous():
+        raise ValueError("restore_project: out is a contiguous fp32 tensor shaped like z, on its device")
+    per = 0 if g_t.numel() == z.numel() else H * W * C
+    call("mulan_restore_project", ptr(z), ptr(net), ptr(g_t), ptr(y), ptr(out), B, H, W, C, int(f), int(bool(gray)),
+         int(mode), per, stream())
+    return out
+
+
 def decode_argmax(z0, g0):
     """uint8 argmax over the 256 decoder bins at z_0 / sqrt(1 - sigmoid(g_0)) (VDM.generate_x, sample_softmax=False)"""
     z0, g0 = _c(z0), _c(g0)

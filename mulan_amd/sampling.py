@@ -21,6 +21,13 @@ alpha_0 x and decode back to the input's integers.  With resample = U > 1 every 
 rounds of: the forward transition q(z_t | z_s) back to t on fresh noise (ops.forward_jump, mulan_forward_jump), the step
 t -> s again at first order, and the mix; the history a repeated step leaves serves the next step as usual.
 The noise of the known region and of the jumps is known_noise_fn(j), j a counter of its own (run_inpaint states the law).
+
+Restoration (range / null-space projection, DDNM): given a measurement y = A x of a degradation whose groups of
+sub-pixels A averages -- super-resolution 'sr:f', colourisation 'gray', or both -- the prediction x_hat of every step is
+replaced by x_hat' = x_hat + A+ (y - A x_hat) (ops.restore_project, mulan_restore_project) and the step runs on x_hat' as
+a data prediction (mode 2 of the same step kernels); the multistep history is x_hat'.  The projection lives in data
+space, so the different schedules inside a group do not enter.  resample = U > 1 is DDNM's time travel: U - 1 rounds of
+jump and first-order step after every step but the last (run_restore).
 """
 import numpy as np
 import torch
@@ -126,6 +133,44 @@ def check_inpaint(sampler, known, mask, resample=1):
     return True
 
 
+DEGRADATION_GRAMMAR = "'sr:f', 'gray' or 'sr:f+gray' with f one of 2, 4, 8, 16"
+
+
+def parse_degradation(spec):
+    """a degradation named in words -> (f, gray): 'sr:f' (f x f average pooling per channel, f in 2, 4, 8, 16) -> (f, False);
+    'gray' (the channel mean) -> (1, True); 'sr:f+gray' (both) -> (f, True).  A pair (f, gray) passes through checked."""
+    if isinstance(spec, (tuple, list)) and len(spec) == 2:
+        f, gray = spec
+        if not isinstance(f, bool) and f in ops.RESTORE_FACTORS + (1,) and (gray or f != 1):
+            return int(f), bool(gray)
+    elif isinstance(spec, str):
+        sr, plus, tail = spec.partition("+")
+        if spec == "gray":
+            return 1, True
+        kind, colon, arg = sr.partition(":")
+        if kind == "sr" and colon and arg in tuple(str(f) for f in ops.RESTORE_FACTORS) and (not plus or tail == "gray"):
+            return int(arg), bool(plus)
+    raise ValueError(f"degradation {spec!r}: expected {DEGRADATION_GRAMMAR}")
+
+
+def check_restore(sampler, measurement, degradation, resample=1, known=None, mask=None):
+    """-> whether the run restores: the measurement and its degradation go together, belong to the few-step samplers, and
+    exclude inpainting (a known image or a mask); resample must be an integer >= 1 either way"""
+    check_sampler(sampler)
+    check_resample(resample)
+    if (measurement is None) != (degradation is None):
+        raise ValueError("restoration needs the measurement and its degradation together")
+    if measurement is None:
+        return False
+    if sampler not in FAST_SAMPLERS:
+        raise ValueError(f"restoration runs with the few-step samplers ({', '.join(FAST_SAMPLERS)}); "
+                         f"the {sampler!r} sampler takes no measurement")
+    if known is not None or mask is not None:
+        raise ValueError("a mask and a measurement in one run are not supported: inpaint or restore")
+    parse_degradation(degradation)
+    return True
+
+
 def mask_from_spec(spec):
     """a mask named in words -> bool [32, 32] (True = keep):
     'box:y0,x0,y1,x1'  the rows y0 .. y1 - 1 and columns x0 .. x1 - 1 are unknown, the rest is kept
@@ -172,9 +217,14 @@ class EagerStepper:
     one standard normal per element for step k (the fifth argument of the call).
     known / mask (both or neither; shaped like z, the image as ops.encode_u8 gives it and one byte per element): the
     inpainting stepper, whose steps end with the mix at gamma_s on known_noise_fn(j) (the call's `mix` argument names
-    j; ZERO_NOISE: the noiseless mix of the last step), and which has mix() for z_1 and jump() for the resampling."""
+    j; ZERO_NOISE: the noiseless mix of the last step), and which has mix() for z_1 and jump() for the resampling.
+    measurement / degradation (both or neither, and not with a mask): the restoring stepper.  Its step is net ->
+    ops.restore_project -> the step kernel at mode 2 on x_hat', which is also the history it keeps; measurement: fp32
+    shaped ops.restore_y_shape, in the scale of ops.encode_u8; hwc = (H, W, C) where z is not [B, H, W, C]; jump() as
+    above, on known_noise_fn(j) (needed for resample > 1 only)."""
 
-    def __init__(self, net_fn, gamma_fn, mode, step_eta=0.0, noise_fn=None, known=None, mask=None, known_noise_fn=None):
+    def __init__(self, net_fn, gamma_fn, mode, step_eta=0.0, noise_fn=None, known=None, mask=None, known_noise_fn=None,
+                 measurement=None, degradation=None, hwc=None):
         self.net_fn, self.gamma_fn, self.mode = net_fn, gamma_fn, int(mode)
         self.step_eta, self.noise_fn = float(step_eta), noise_fn
         if self.step_eta > 0.0 and noise_fn is None:
@@ -182,12 +232,29 @@ class EagerStepper:
         self.g_prev = self.x_prev = None
         self._g = None              # (t, gamma(t)) of the last step's s: the next step's t
         self.known = self.mask = self.known_noise_fn = None
-        if known is not None or mask is not None or known_noise_fn is not None:
+        restoring = measurement is not None or degradation is not None
+        if known is not None or mask is not None or (known_noise_fn is not None and not restoring):
             self.set_known(known, mask, known_noise_fn)
+        self.measurement = self.degradation = None
+        self.hwc = hwc
+        if restoring:
+            if self.inpaint:
+                raise ValueError("a mask and a measurement in one run are not supported: inpaint or restore")
+            self.set_measurement(measurement, degradation, known_noise_fn)
 
     @property
     def inpaint(self):
         return self.mask is not None
+
+    @property
+    def restore(self):
+        return self.measurement is not None
+
+    def set_measurement(self, measurement, degradation, known_noise_fn=None):
+        if measurement is None or degradation is None:
+            raise ValueError("restoration needs the measurement and its degradation together")
+        self.measurement, self.degradation = measurement, parse_degradation(degradation)
+        self.known_noise_fn = known_noise_fn
 
     def set_known(self, known, mask, known_noise_fn):
         if known is None or mask is None:
@@ -211,6 +278,8 @@ class EagerStepper:
     def jump(self, z, s, t, j):
         """z_t ~ q(z_t | z_s = z) on known_noise_fn(j)"""
         s, t = f32(s), f32(t)
+        if self.known_noise_fn is None:
+            raise ValueError("a jump needs known_noise_fn(j) -> its noise")
         return ops.forward_jump(z, self._gamma(s), self.gamma_fn(t), self.known_noise_fn(j))
 
     def __call__(self, z, t, s, order, k=None, mix=None):
@@ -219,17 +288,19 @@ class EagerStepper:
         t, s = f32(t), f32(s)
         g_t = self._gamma(t)
         g_s = self.gamma_fn(s)
-        net = self.net_fn(z, t)
+        net, mode = self.net_fn(z, t), self.mode
+        if self.restore:
+            net = ops.restore_project(z, net, g_t, self.measurement, *self.degradation, mode, self.hwc)
+            mode = 2                # the step runs on x_hat', and its x0 output -- the history -- is x_hat' too
         hist = (self.g_prev, self.x_prev) if order == 2 else (None, None)
         if order == 2 and self.g_prev is None:
             raise RuntimeError("a second-order step needs the history of a previous step")
         if self.step_eta > 0.0:
             if k is None:
                 raise ValueError("a stochastic step needs its index k (the noise is drawn per step)")
-            z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, self.mode, self.noise_fn(k), self.step_eta,
-                                                      *hist)
+            z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, mode, self.noise_fn(k), self.step_eta, *hist)
         else:
-            z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, self.mode, *hist)
+            z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, mode, *hist)
         if mix is not None:
             z_s = ops.inpaint_mix(z_s, self.known, self.mask, g_s, self._known_xi(mix), out=z_s)
         self.g_prev, self.x_prev, self._g = g_t, x0, (s, g_s)
@@ -239,14 +310,16 @@ class EagerStepper:
 def run(stepper, z, grid, orders, resample=1, known=None, mask=None, known_noise_fn=None):
     """the solver loop: stepper(z, t, s, order, k) -> z_s along the grid; the step's index k selects the noise of a
     stochastic step.  known / mask / known_noise_fn: handed to the stepper (set_known); a stepper that inpaints runs
-    run_inpaint with `resample`"""
+    run_inpaint with `resample`, one that restores (a measurement) run_restore"""
     assert len(orders) == len(grid) - 1
     if known is not None or mask is not None:
         stepper.set_known(known, mask, known_noise_fn)
     if getattr(stepper, "inpaint", False):
         return run_inpaint(stepper, z, grid, orders, resample)
+    if getattr(stepper, "restore", False):
+        return run_restore(stepper, z, grid, orders, resample)
     if check_resample(resample) != 1:
-        raise ValueError("resample applies to inpainting (a known image and a mask)")
+        raise ValueError("resample applies to inpainting (a known image and a mask) and to restoration (a measurement)")
     for k, order in enumerate(orders):
         z = stepper(z, grid[k], grid[k + 1], order, k)
     return z
@@ -280,18 +353,41 @@ def run_inpaint(stepper, z, grid, orders, resample=1):
     return z
 
 
+def run_restore(stepper, z, grid, orders, resample=1):
+    """the solver loop of a restoring stepper (every step projects its prediction onto the measurement): run_inpaint
+    without the mixes.  With resample = U > 1 every step but the last is followed by U - 1 rounds of jump s -> t (DDNM's
+    time travel) and the step t -> s again at first order.  The jumps take known_noise_fn(j), j = 0, 1, 2, ... in the
+    order they run; a run with U = 1 draws nothing from it.  Round r = 1 .. U - 1 of step k draws the noise of its
+    stochastic step under the step index k + r N (N steps), as run_inpaint does."""
+    U, N = check_resample(resample), len(orders)
+    j = 0
+    for k, order in enumerate(orders):
+        t, s = grid[k], grid[k + 1]
+        z = stepper(z, t, s, order, k)
+        if k < N - 1:
+            for r in range(1, U):
+                z = stepper.jump(z, s, t, j)
+                j += 1
+                z = stepper(z, t, s, 1, k + r * N)
+    return z
+
+
 def sample(net_fn, gamma_fn, z, mode, sampler="dpm2m", steps=None, t_grid=None, eta=0.0, noise_fn=None, known=None,
-           mask=None, known_noise_fn=None, resample=1):
+           mask=None, known_noise_fn=None, resample=1, measurement=None, degradation=None, hwc=None):
     """z_0 from z_1 = z by `sampler` (ddim | dpm2m | sde2m) over `steps` uniform steps or the explicit `t_grid`; mode as
     ops.fast_sampler_step (0: net_fn gives the velocity, 1: eps_hat, 2: x_hat).  eta (ddim only): 0 is the
     deterministic sampler; sde2m and ddim with eta > 0 need noise_fn(k) -> xi shaped like z, the noise of step k.
     known, mask (shaped like z: the image as ops.encode_u8 gives it, one byte per element, non-zero = keep): inpainting
     with `resample` passes per step, on known_noise_fn(j) -> xi shaped like z (run_inpaint states which j is drawn
-    when)"""
+    when).
+    measurement, degradation (a spec of parse_degradation, or its pair): restoration instead, the measurement fp32
+    shaped ops.restore_y_shape in the scale of ops.encode_u8; z is [B, H, W, C] or hwc names (H, W, C); `resample`
+    passes per step on known_noise_fn(j), the noise of jump j (run_restore)"""
     step_eta = check_eta(sampler, eta)
-    check_inpaint(sampler, known, mask, resample)
+    restore = check_restore(sampler, measurement, degradation, resample, known, mask)
+    check_inpaint(sampler, known, mask, 1 if restore else resample)
     grid = time_grid(steps, t_grid)
     orders = step_orders(sampler, len(grid) - 1)
     with torch.no_grad():
-        return run(EagerStepper(net_fn, gamma_fn, mode, step_eta, noise_fn, known, mask, known_noise_fn), z, grid,
-                   orders, resample)
+        return run(EagerStepper(net_fn, gamma_fn, mode, step_eta, noise_fn, known, mask, known_noise_fn, measurement,
+                                degradation, hwc), z, grid, orders, resample)

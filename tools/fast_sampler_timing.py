@@ -3,12 +3,14 @@ does not depend on them).  Forms, alternated within one run after one untimed wa
   ancestral T = 1000 (replayed reverse step), ddim N = 50 (replayed), dpm2m N = 25 replayed, dpm2m N = 25 eager,
   sde2m N = 25 replayed (the stochastic step: one randn and one more read of the latent's size per step);
   with --inpaint also dpm2m N = 25 replayed under a half:left mask at resample 1 (25 network evaluations, one mix per
-  step) and at resample 2 (49 evaluations, a jump and a mix more per repeated step).
+  step) and at resample 2 (49 evaluations, a jump and a mix more per repeated step);
+  with --restore also dpm2m N = 25 replayed under an sr:4 measurement at resample 1 (25 evaluations, one projection per
+  step).
 Each time is one batch from z_1 to the uint8 images (the loop plus generate_x) with the stepper built beforehand (what
 `python -m ldm.sample` pays per batch), between two device synchronisations.  One JSON line per timed batch, then a
 summary line (median ms per batch).
 
-    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3] [--few-step-only] [--inpaint]
+    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3] [--few-step-only] [--inpaint] [--restore]
 """
 import argparse
 import json
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--few-step-only", action="store_true", help="leave the 1000-step ancestral form out")
     ap.add_argument("--inpaint", action="store_true", help="add dpm2m with a mask at resample 1 and 2")
+    ap.add_argument("--restore", action="store_true", help="add dpm2m with an sr:4 measurement at resample 1")
     args = ap.parse_args()
     import torch
     from mulan_amd.config import load_config_file
@@ -80,6 +83,14 @@ def main():
                 params, z1, ctx, "dpm2m", 25, stepper=mask_replay, known=known, mask=mask, resample=U,
                 known_noise=rng.fold_in(2)), ctx["coeffs"])
         forms += [("dpm2m_N25_inpaint_resample1_replayed", inpaint(1)), ("dpm2m_N25_inpaint_resample2_replayed", inpaint(2))]
+    if args.restore:
+        from mulan_amd import ops
+        with torch.no_grad():
+            restore_replay = model.fast_stepper(params, B, dev, ctx, graph=True, restore="sr:4")
+        assert type(restore_replay).__name__ == "GraphedFastStep"
+        y = ops.restore_measure(ops.encode_u8(torch.randint(0, 256, (B, 32, 32, 3), dtype=torch.uint8, device=dev)), 4, False)
+        forms += [("dpm2m_N25_restore_sr4_replayed", lambda: model.generate_x(params, model.fast_sample(
+            params, z1, ctx, "dpm2m", 25, stepper=restore_replay, measurement=y, degradation="sr:4"), ctx["coeffs"]))]
     if args.few_step_only:
         forms = forms[1:]
     times = {name: [] for name, _ in forms}
