@@ -130,7 +130,7 @@ class Experiment_Colab(Experiment_VDM):
         known, mask (optional, one per key: uint8 [batch_size, 32, 32, 3] and a mask as draw_samples takes it; one
         mask alone serves every batch): inpainting, `resample` passes per step.  The noise of the known region and of
         the jumps comes from a fourth sub-key, key.fold_in(KNOWN_NOISE_FOLD), folded with the draw's own counter
-        (sampling.run_inpaint); the three sub-keys above and their draws are as without a mask.  Inpainting also takes
+        (sampling.run); the three sub-keys above and their draws are as without a mask.  Inpainting also takes
         embedding 'encoder' (the hard top-k of apply_encoder on the images with the unknown pixels set to 128) or an
         explicit k-hot tensor [50] or [batch_size, 50].
         measurement (one per key: fp32 in the scale of ops.encode_u8, shaped ops.restore_y_shape) and degradation
@@ -139,10 +139,8 @@ class Experiment_Colab(Experiment_VDM):
         of inpainting apply, 'encoder' on the replicated measurement A+ y rounded to 8-bit levels."""
         sampling.check_eta(sampler, eta)
         keys = list(keys)
-        restore = sampling.check_restore(sampler, measurement, degradation, resample, known, mask)
-        inpaint = sampling.check_inpaint(sampler, known, mask, 1 if restore else resample)
-        if restore:
-            restore = sampling.parse_degradation(degradation)
+        inpaint, restore, resample = sampling.check_guidance(sampler, known, mask, measurement, degradation, resample)
+        if restore is not None:
             if torch.is_tensor(measurement) or isinstance(measurement, np.ndarray) or len(measurement) != len(keys):
                 raise ValueError(f"{len(keys)} keys need a list of {len(keys)} measurements, one per batch")
         if inpaint:
@@ -150,18 +148,19 @@ class Experiment_Colab(Experiment_VDM):
                 mask = [mask] * len(keys)
             if len(known) != len(keys) or len(mask) != len(keys):
                 raise ValueError(f"{len(keys)} keys, but {len(known)} batches of known images and {len(mask)} masks")
-        self._check_embedding(embedding, batch_size, inpaint or bool(restore))
+        self._check_embedding(embedding, batch_size, inpaint or restore is not None)
         out, stepper = [], None
         for b, key in enumerate(keys):
             k_z, k_e, k_s = key.split(3)
-            kw = {}
-            if inpaint:
-                kw = dict(known=known[b], mask=mask[b], resample=resample, known_rng=key.fold_in(self.KNOWN_NOISE_FOLD))
-            if restore:
-                kw = dict(measurement=measurement[b], degradation=degradation, resample=resample,
-                          known_rng=key.fold_in(self.KNOWN_NOISE_FOLD))
+            kw = {}                                  # what guides batch b: a measurement, or a known image, or nothing
+            if restore is not None:
+                kw = dict(measurement=measurement[b], degradation=degradation)
+            elif inpaint:
+                kw = dict(known=known[b], mask=mask[b])
+            if kw:
+                kw.update(resample=resample, known_rng=key.fold_in(self.KNOWN_NOISE_FOLD))
             emb = self._batch_embedding(embedding, k_e, batch_size, kw.get("known"), kw.get("mask"),
-                                        kw.get("measurement"), restore or None)
+                                        kw.get("measurement"), restore)
             x, stepper = self.draw_samples(self.params, batch_size, emb, k_z, k_s, key.fold_in(steps), sampler, steps,
                                            prior_scale=float(self.config.model.sigma_prior), stepper=stepper, eta=eta,
                                            **kw)
@@ -171,7 +170,7 @@ class Experiment_Colab(Experiment_VDM):
     def inpaint(self, images, mask, embedding='deterministic', sampler='sde2m', steps=25, eta=0.0, resample=1, rng=None):
         """uint8 [B, 32, 32, 3]: `images` (uint8 [B, 32, 32, 3]) with the sub-pixels outside `mask` (bool or uint8
         [32, 32], [B, 32, 32] or [B, 32, 32, 3], True = keep) drawn by a few-step sampler (ddim with eta, dpm2m, sde2m)
-        that overwrites the kept ones after every step with their own alpha_t x + sigma_t eps (sampling.run_inpaint;
+        that overwrites the kept ones after every step with their own alpha_t x + sigma_t eps (sampling.run;
         resample > 1: that many passes per step).  With argmax decoding (sample_softmax False) the kept sub-pixels come
         back as they went in, with no paste-over.  embedding: 'deterministic', 'random', 'encoder' (MuLAN models: the hard
         top-k of apply_encoder on the images with the unknown pixels set to 128) or a k-hot tensor [50] or [B, 50].
@@ -187,7 +186,7 @@ class Experiment_Colab(Experiment_VDM):
     def restore(self, images=None, measurement=None, degradation='sr:4', embedding='deterministic', sampler='sde2m',
                 steps=25, eta=0.0, resample=1, rng=None):
         """(restored uint8 [B, 32, 32, 3], residual fp32 [B]): images consistent with a degraded observation, drawn by a
-        few-step sampler whose every prediction is projected onto the measurement (sampling.run_restore).
+        few-step sampler whose every prediction is projected onto the measurement (sampling.run).
         degradation: 'sr:f' (the f x f average-pooled image, f in 2, 4, 8, 16), 'gray' (the channel mean) or 'sr:f+gray'.
         Exactly one of: images (uint8 [B, 32, 32, 3]), which are degraded here (ops.restore_measure on their encoding),
         or measurement ([B, 32 / f, 32 / f, 3 or 1 with gray]; fp32 in the scale of ops.encode_u8, or uint8 levels, which

@@ -605,21 +605,19 @@ class Experiment_VDM(Experiment):
         model.fast_sample, the stepper re-used when one is given (re-targeted at this batch's context) and returned for
         the next batch; sde2m and ddim with eta > 0 draw the noise of step k under step_rng.fold_in(k) as well.
         known (uint8 [B, 32, 32, 3]) and mask (bool or uint8 [32, 32], [B, 32, 32] or [B, 32, 32, 3], True = keep; it
-        is broadcast to one byte per sub-pixel): inpainting with the few-step samplers (sampling.run_inpaint), `resample`
+        is broadcast to one byte per sub-pixel): inpainting with the few-step samplers (sampling.run), `resample`
         passes per step.  The noise of the known region and of the jumps comes from known_rng alone, a key that neither
         z_1 nor the step noise uses: draw j under known_rng.fold_in(j).  With argmax decoding the kept sub-pixels of
         the result are the input's, with no paste-over.
         measurement (fp32, in the scale of ops.encode_u8, shaped ops.restore_y_shape(B, 32, 32, 3, f, gray)) and
-        degradation ('sr:f', 'gray', 'sr:f+gray'): restoration with the few-step samplers instead (sampling.run_restore):
+        degradation ('sr:f', 'gray', 'sr:f+gray'): restoration with the few-step samplers instead (sampling.run):
         every step's prediction is projected onto the measurement.  resample > 1 draws jump j under known_rng.fold_in(j);
         resample = 1 draws nothing from known_rng and needs none.  A mask and a measurement in one run are refused.
         -> (uint8 [B, 32, 32, 3], stepper or None)"""
         step_eta = sampling.check_eta(sampler, eta)          # what the steps run with: 1 for sde2m
-        restore = sampling.check_restore(sampler, measurement, degradation, resample, known, mask)
-        inpaint = sampling.check_inpaint(sampler, known, mask, 1 if restore else resample)
-        if restore:
-            restore = sampling.parse_degradation(degradation)
-            if sampling.check_resample(resample) > 1 and known_rng is None:
+        inpaint, restore, resample = sampling.check_guidance(sampler, known, mask, measurement, degradation, resample)
+        if restore is not None:
+            if resample > 1 and known_rng is None:
                 raise ValueError("draw_samples: resample > 1 needs known_rng, the key of the jumps' noise")
             measurement = torch.as_tensor(measurement)
             if measurement.dtype != torch.float32:
@@ -658,15 +656,15 @@ class Experiment_VDM(Experiment):
                     ctx = self.model.fast_context(params, embedding if mulan else None, conditioning)
                     if stepper is None:
                         stepper = self.model.fast_stepper(params, B, self.device, ctx, step_eta=step_eta,
-                                                          inpaint=inpaint, restore=restore or None)
-                    kw = {}
-                    if restore:
-                        kw = dict(measurement=measurement.to(self.device), degradation=restore, resample=resample,
-                                  known_noise=known_rng)
-                    if inpaint:
+                                                          inpaint=inpaint, restore=restore)
+                    kw = {}                          # what guides the run: a measurement, or a known image, or nothing
+                    if restore is not None:
+                        kw = dict(measurement=measurement.to(self.device), degradation=restore)
+                    elif inpaint:
                         from . import ops
-                        kw = dict(known=ops.encode_u8(known.to(self.device)).reshape(B, 3072), mask=mask,
-                                  resample=resample, known_noise=known_rng)
+                        kw = dict(known=ops.encode_u8(known.to(self.device)).reshape(B, 3072), mask=mask)
+                    if kw:
+                        kw.update(resample=resample, known_noise=known_rng)
                     z = self.model.fast_sample(params, z, ctx, sampler, None if t_grid is not None else steps, t_grid,
                                                stepper=stepper, eta=eta, noise=step_rng if step_eta > 0.0 else None,
                                                **kw)

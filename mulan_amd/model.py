@@ -234,47 +234,59 @@ def _check_fast_context(like, ctx):
                                  f"stepper was built for {None if x is None else tuple(x.shape)}")
 
 
-def _fill_step_noise(buf, noise, k):
-    """the noise of step k of a stochastic few-step sampler into buf [B, 3072]: `noise` is the batch's step key (the
-    draw is ops.randn under key.fold_in(k), as the ancestral steppers draw theirs) or a callable k -> xi"""
-    if noise is None:
-        raise RuntimeError("a stochastic step needs the batch's noise (set_noise: a Key, or a callable k -> xi)")
-    if k is None:
-        raise ValueError("a stochastic step needs its index k (the noise is drawn per step)")
-    if callable(noise):
-        buf.copy_(noise(k).reshape(buf.shape))
-    else:
-        ops.randn(None, noise.fold_in(k).v, 0, buf.device, out=buf)
-    return buf
-
-
-def _fill_known_noise(buf, noise, j):
-    """draw j of an inpainting run -- the noise of the known region at a mix, or of a jump -- into buf [B, 3072]:
-    `noise` is the batch's known-region key (ops.randn under key.fold_in(j)) or a callable j -> xi;
-    j = sampling.ZERO_NOISE: zeros (the mix of the last step)"""
-    if j < 0:
+def _fill_noise(buf, noise, i, missing, zeros=False):
+    """draw i of a few-step run into buf [B, 3072]: `noise` is a key of the batch (the draw is ops.randn under
+    key.fold_in(i), as the ancestral steppers draw theirs) or a callable i -> xi; `missing`: what to say where the batch
+    has set none.  zeros: a negative i (sampling.ZERO_NOISE, the mix of the last step) fills zeros"""
+    if zeros and i < 0:
         return buf.zero_()
     if noise is None:
-        raise RuntimeError("inpainting needs the batch's known-region noise (set_known: a Key, or a callable j -> xi)")
+        raise RuntimeError(missing)
+    if i is None:
+        raise ValueError("a stochastic step needs its index k (the noise is drawn per step)")
     if callable(noise):
-        buf.copy_(noise(j).reshape(buf.shape))
+        buf.copy_(noise(i).reshape(buf.shape))
     else:
-        ops.randn(None, noise.fold_in(j).v, 0, buf.device, out=buf)
+        ops.randn(None, noise.fold_in(i).v, 0, buf.device, out=buf)
     return buf
 
 
-class _KnownBuffers:
-    """What an inpainting stepper keeps per batch in static buffers: the known image x [B, 3072] (as ops.encode_u8
-    gives it), the mask (one byte per sub-pixel, non-zero = keep) and the noise of the known region for the mix;
-    set_known() fills the first two and names the key (or callable) that noise, and a jump's, is drawn from."""
+class _FastStepState:
+    """What the two steppers of the few-step samplers keep per batch, in static buffers [B, 3072] where a kernel reads it:
+    step_eta > 0: the noise xi of the stochastic step, drawn for step k from the key (or callable) set_noise() names;
+    inpaint: the known image (as ops.encode_u8 gives it) and the mask (one byte per sub-pixel, non-zero = keep) of
+    set_known(); restore = (f, gray): the measurement y (shaped ops.restore_y_shape) of set_measurement().  kxi takes
+    draw j of the key (or callable) either of the two names: the noise of the known region at a mix and of a jump, one
+    buffer for both in both steppers (a jump's noise is read before the next mix is drawn)."""
 
-    def _init_known(self, B, device, inpaint):
-        self.inpaint, self.known_noise = bool(inpaint), None
-        self.known = self.mask = self.kxi = None
-        if self.inpaint:
-            f32 = dict(device=device, dtype=torch.float32)
-            self.known, self.mask = torch.zeros((B, D), **f32), torch.zeros((B, D), device=device, dtype=torch.uint8)
-            self.kxi = torch.zeros((B, D), **f32)
+    def __init__(self, B, device, step_eta, inpaint, restore):
+        from . import sampling
+        self.B, self.step_eta, self.inpaint = B, float(step_eta), bool(inpaint)
+        self.restore = None if restore is None else sampling.parse_degradation(restore)
+        if self.inpaint and self.restore is not None:
+            raise ValueError("a mask and a measurement in one run are not supported: inpaint or restore")
+        f32 = lambda on, *shape: torch.zeros(shape or (B, D), device=device, dtype=torch.float32) if on else None
+        self.noise = self.known_noise = None
+        self.xi, self.known = f32(self.step_eta > 0.0), f32(self.inpaint)
+        self.mask = torch.zeros((B, D), device=device, dtype=torch.uint8) if self.inpaint else None
+        self.kxi = f32(self.inpaint or self.restore is not None)
+        self.y = None if self.restore is None else f32(True, *ops.restore_y_shape(B, *HWC, *self.restore))
+
+    def check_serves(self, step_eta, inpaint, restore):
+        """a stepper serves the runs it was built for: the same step_eta, with or without a mask, the same degradation"""
+        if self.step_eta != step_eta:
+            raise ValueError(f"fast_sample: the stepper's steps run with eta = {self.step_eta}, this run asks for "
+                             f"{step_eta}")
+        if self.inpaint != inpaint:
+            raise ValueError("fast_sample: the stepper was built %s a mask, this run comes %s one"
+                             % (("without", "with") if inpaint else ("with", "without")))
+        if self.restore != restore:
+            name = lambda r: "no degradation" if r is None else f"the degradation (f, gray) = {r}"
+            raise ValueError(f"fast_sample: the stepper was built for {name(self.restore)}, this run comes with "
+                             f"{name(restore)}")
+
+    def set_noise(self, noise):
+        self.noise = noise
 
     def set_known(self, known, mask, noise=None):
         """this batch's known image and mask (B x 3072 elements each) and its known-region noise"""
@@ -287,21 +299,6 @@ class _KnownBuffers:
         self.mask.copy_(mask.reshape(self.mask.shape))
         self.known_noise = noise
 
-    def _check_mix(self, mix):
-        if (mix is not None) != self.inpaint:
-            raise ValueError("a stepper built with a mask mixes after every step, and one built without never does")
-
-    # a restoring stepper (sampling.run_restore) keeps the measurement y of its degradation (f, gray) in a static buffer
-    # shaped ops.restore_y_shape, set per batch, and draws the noise of its jumps from the key set_measurement() names
-    def _init_measurement(self, B, device, restore):
-        from . import sampling
-        self.restore = None if restore is None else sampling.parse_degradation(restore)
-        self.y = None
-        if self.restore is not None:
-            if self.inpaint:
-                raise ValueError("a mask and a measurement in one run are not supported: inpaint or restore")
-            self.y = torch.zeros(ops.restore_y_shape(B, *HWC, *self.restore), device=device, dtype=torch.float32)
-
     def set_measurement(self, y, noise=None):
         """this batch's measurement (fp32, ops.restore_y_shape values) and the key (or callable j -> xi) of its jumps"""
         if self.restore is None:
@@ -312,38 +309,41 @@ class _KnownBuffers:
         self.y.copy_(y.reshape(self.y.shape))
         self.known_noise = noise
 
+    def _check_mix(self, mix):
+        if (mix is not None) != self.inpaint:
+            raise ValueError("a stepper built with a mask mixes after every step, and one built without never does")
 
-class EagerFastStep(_KnownBuffers):
+    def _step_xi(self, k):
+        return _fill_noise(self.xi, self.noise, k,
+                           "a stochastic step needs the batch's noise (set_noise: a Key, or a callable k -> xi)")
+
+    def _known_xi(self, j):
+        return _fill_noise(self.kxi, self.known_noise, j, "inpainting needs the batch's known-region noise (set_known: a "
+                           "Key, or a callable j -> xi)", zeros=True)
+
+
+class EagerFastStep(_FastStepState):
     """The eager form of GraphedFastStep (MULAN_SAMPLER_GRAPH=0, or a failed capture): sampling.EagerStepper over the
-    model's network and schedule, reading the context through this object so that set_context() re-targets it at the
-    next batch like the replayed stepper.  step_eta > 0 (sampling.check_eta): the stochastic step on the noise
-    set_noise() names.  inpaint: the stepper of an inpainting run (sampling.run_inpaint) on what set_known() holds.
-    restore = (f, gray): the stepper of a restoring run (sampling.run_restore) on what set_measurement() holds."""
+    model's network and schedule and over the buffers of _FastStepState, reading the context through this object so that
+    set_context() re-targets it at the next batch like the replayed stepper.  It shares no step code with the replayed
+    form beyond sampling.solver_step: gamma(s) is cached for the next step, and the history is the step's own output."""
 
     def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False, restore=None):
         from . import sampling
-        self.ctx, self.step_eta, self.noise = ctx, float(step_eta), None
-        self._init_known(B, device, inpaint)
-        self._init_measurement(B, device, restore)
-        if self.restore is not None:
-            self.kxi = torch.zeros((B, D), device=device, dtype=torch.float32)      # the noise of a jump
+        super().__init__(B, device, step_eta, inpaint, restore)
+        self.ctx = ctx
         times = lambda t: torch.full((B,), float(np.float32(t)), device=device, dtype=torch.float32)
         gamma_fn = lambda t: model._fast_gamma(params, self.ctx, times(t))
         net_fn = lambda z, t: model._fast_net(params, z.reshape(B, D), gamma_fn(t), self.ctx).view(z.shape)
-        self.xi = torch.zeros((B, D), device=device, dtype=torch.float32) if self.step_eta > 0.0 else None
-        noise_fn = (lambda k: _fill_step_noise(self.xi, self.noise, k)) if self.step_eta > 0.0 else None
-        known_fn = (lambda j: _fill_known_noise(self.kxi, self.known_noise, j)) if self.kxi is not None else None
-        self._make = lambda: sampling.EagerStepper(net_fn, gamma_fn, model._fast_mode(), self.step_eta, noise_fn,
-                                                   self.known, self.mask, known_fn, self.y, self.restore, HWC)
+        self._make = lambda: sampling.EagerStepper(
+            net_fn, gamma_fn, model._fast_mode(), self.step_eta, self._step_xi if self.xi is not None else None, self.known,
+            self.mask, self._known_xi if self.kxi is not None else None, self.y, self.restore, HWC)
         self._step = self._make()
 
     def set_context(self, ctx):
         _check_fast_context(self.ctx, ctx)
         self.ctx = ctx
         self._step = self._make()             # no history and no cached gamma of the previous batch
-
-    def set_noise(self, noise):
-        self.noise = noise
 
     def mix(self, z, t, j):
         return self._step.mix(z, t, j)
@@ -356,7 +356,7 @@ class EagerFastStep(_KnownBuffers):
         return self._step(z, t, s, order, k, mix)
 
 
-class GraphedFastStep(_KnownBuffers):
+class GraphedFastStep(_FastStepState):
     """One step of the deterministic few-step samplers (DDIM / DPM-Solver++(2M), mulan_amd.sampling) captured as a HIP
     graph and replayed N times.  What changes from step to step reaches the kernels through static buffers written
     before each replay: z_t, the two times t, s and the history (the previous step's gamma and x_hat, copied from the
@@ -367,31 +367,26 @@ class GraphedFastStep(_KnownBuffers):
     (tests/test_gpu_fast_sampler.py::test_replayed_fast_step_equals_the_eager_step).  The weights must stay as they are
     while the stepper lives (the caller holds the ParamPacker refresh).
     step_eta > 0 captures the stochastic step (DDIM with eta, SDE-DPM-Solver++(2M)) instead: its noise xi is one more static
-    buffer, filled before each replay by the Philox call of the eager stepper (_fill_step_noise, the pattern of
+    buffer, filled before each replay by the Philox call of the eager stepper (_fill_noise, the pattern of
     GraphedReverseStep.step); step_eta is an argument of the captured launch, so a stepper serves the one it was built
     for.
     inpaint captures the mix behind the step kernel (mulan_inpaint_mix at gamma_s): the known image, the mask and the
     known region's noise are static buffers, the first two set per batch (set_known), the noise filled before each
-    replay (_fill_known_noise; zeros for the last step, which the kernel reads as it reads a NULL xi).  The mix of z_1
-    and the jumps of the resampling are eager launches between replays, the jump on a static noise buffer of its own.
+    replay (zeros for the last step, which the kernel reads as it reads a NULL xi).  The mix of z_1 and the jumps of the
+    resampling are eager launches between replays, on the same noise buffer.
     restore = (f, gray) captures the projection (mulan_restore_project) between the network and the step kernel, which
     then runs at mode 2 on x_hat'; the measurement is a static buffer set per batch (set_measurement), and the history
     copied after each replay is x_hat'.  The jumps are eager launches as above."""
 
     def __init__(self, model, params, B, device, ctx, step_eta=0.0, inpaint=False, restore=None):
-        self.B, self.step_eta, self.noise = B, float(step_eta), None
+        super().__init__(B, device, step_eta, inpaint, restore)
         self.model, self.params = model, params
-        self._init_known(B, device, inpaint)
-        self._init_measurement(B, device, restore)
         f32 = dict(device=device, dtype=torch.float32)
-        jumps = self.inpaint or self.restore is not None
-        self.jxi = torch.zeros((B, D), **f32) if jumps else None              # the noise of a jump
         self.ctx = {k: (None if v is None else tuple(c.detach().clone() for c in v) if isinstance(v, tuple)
                         else v.detach().clone()) for k, v in ctx.items()}
         self.z_in, self.x_prev = torch.zeros((B, D), **f32), torch.zeros((B, D), **f32)
         self.t, self.s = torch.full((B,), 1.0, **f32), torch.full((B,), 0.5, **f32)
         self.g_prev = torch.full(model._fast_gamma_shape(B), float("nan"), **f32)
-        self.xi = torch.zeros((B, D), **f32) if self.step_eta > 0.0 else None
         run = lambda: model._fast_step(params, self.z_in, self.t, self.s, self.g_prev, self.x_prev, self.ctx, self.xi,
                                        self.step_eta, self.known, self.mask, self.kxi, self.y, self.restore)
         with torch.no_grad():
@@ -408,31 +403,26 @@ class GraphedFastStep(_KnownBuffers):
                 self.ctx[k].copy_(v)
         self.has_history = False
 
-    def set_noise(self, noise):
-        self.noise = noise
-
     def _gamma_at(self, buf, t):
         buf.fill_(float(np.float32(t)))
         return self.model._fast_gamma(self.params, self.ctx, buf)
 
     def mix(self, z, t, j):
         g = self._gamma_at(self.t, t)
-        _fill_known_noise(self.kxi, self.known_noise, j)
-        return ops.inpaint_mix(z.reshape(self.B, D), self.known, self.mask, g, self.kxi).view(z.shape)
+        return ops.inpaint_mix(z.reshape(self.B, D), self.known, self.mask, g, self._known_xi(j)).view(z.shape)
 
     def jump(self, z, s, t, j):
         g_s, g_t = self._gamma_at(self.s, s), self._gamma_at(self.t, t)
-        _fill_known_noise(self.jxi, self.known_noise, j)
-        return ops.forward_jump(z.reshape(self.B, D), g_s, g_t, self.jxi).view(z.shape)
+        return ops.forward_jump(z.reshape(self.B, D), g_s, g_t, self._known_xi(j)).view(z.shape)
 
     def __call__(self, z, t, s, order, k=None, mix=None):
         self._check_mix(mix)
         if order == 2 and not self.has_history:
             raise RuntimeError("a second-order step needs the history of a previous step")
         if self.xi is not None:
-            _fill_step_noise(self.xi, self.noise, k)
+            self._step_xi(k)
         if mix is not None:
-            _fill_known_noise(self.kxi, self.known_noise, mix)
+            self._known_xi(mix)
         self.z_in.copy_(z.reshape(self.B, D))
         self.t.fill_(float(np.float32(t)))
         self.s.fill_(float(np.float32(s)))
@@ -776,18 +766,11 @@ class _VDMBase:
         of z_s are then replaced by alpha_s known + sigma_s known_xi (known_xi None: zero noise); measurement with
         restore = (f, gray): the prediction is projected onto the measurement and the step runs on x_hat' at mode 2, so
         the x_hat_t returned is x_hat'"""
+        from . import sampling
         g_t = self._fast_gamma(params, ctx, t)
         g_s = self._fast_gamma(params, ctx, s)
-        net, mode = self._fast_net(params, z, g_t, ctx), self._fast_mode()
-        if restore is not None:
-            net, mode = ops.restore_project(z, net, g_t, measurement, *restore, mode, HWC), 2
-        if xi is not None:
-            z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, mode, xi, step_eta, g_prev,
-                                                      x_prev)
-        else:
-            z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, mode, g_prev, x_prev)
-        if mask is not None:
-            z_s = ops.inpaint_mix(z_s, known, mask, g_s, known_xi, out=z_s)
+        z_s, x0 = sampling.solver_step(z, self._fast_net(params, z, g_t, ctx), g_t, g_s, self._fast_mode(),
+                                       (g_prev, x_prev), xi, step_eta, known, mask, known_xi, measurement, restore, HWC)
         return z_s, x0, g_t
 
     def fast_stepper(self, params, B, device, ctx, graph=None, step_eta=0.0, inpaint=False, restore=None):
@@ -813,28 +796,25 @@ class _VDMBase:
         eta: for ddim (0: the deterministic sampler).  noise (sde2m, ddim with eta > 0): the batch's step key -- step k
         draws xi = randn under noise.fold_in(k) -- or a callable k -> xi [B, 3072].
         known (fp32 [B, 3072], the image as ops.encode_u8 gives it) and mask (uint8 or bool [B, 3072], non-zero = keep):
-        inpainting (sampling.run_inpaint) with `resample` passes per step.  known_noise: the batch's known-region key --
-        draw j of the run (the noise of the known region at a mix, or of a jump; run_inpaint states which j is drawn
+        inpainting (sampling.run) with `resample` passes per step.  known_noise: the batch's known-region key --
+        draw j of the run (the noise of the known region at a mix, or of a jump; sampling.run states which j is drawn
         when) is randn under known_noise.fold_in(j) -- or a callable j -> xi [B, 3072].  It is a key of its own: step k
         keeps drawing under noise.fold_in(k), and round r of a resampled step k under noise.fold_in(k + r N).
         measurement (fp32, shaped ops.restore_y_shape(B, 32, 32, 3, f, gray), in the scale of ops.encode_u8) and
-        degradation ('sr:f', 'gray', 'sr:f+gray' or the pair (f, gray)): restoration instead (sampling.run_restore) with
+        degradation ('sr:f', 'gray', 'sr:f+gray' or the pair (f, gray)): restoration instead (sampling.run) with
         `resample` passes per step; jump j of a run with resample > 1 draws under known_noise.fold_in(j), and a run with
         resample = 1 needs no known_noise"""
         from . import sampling
         step_eta = sampling.check_eta(sampler, eta)
-        restoring = sampling.check_restore(sampler, measurement, degradation, resample, known, mask)
-        inpaint = sampling.check_inpaint(sampler, known, mask, 1 if restoring else resample)
+        inpaint, restore, resample = sampling.check_guidance(sampler, known, mask, measurement, degradation, resample)
         B = z.shape[0]
-        restore = None
-        if restoring:
-            restore = sampling.parse_degradation(degradation)
+        if restore is not None:
             shape = ops.restore_y_shape(B, *HWC, *restore)
             if not torch.is_tensor(measurement) or measurement.dtype != torch.float32 or tuple(measurement.shape) != shape:
                 got = (f"{measurement.dtype} {list(measurement.shape)}" if torch.is_tensor(measurement)
                        else type(measurement).__name__)
                 raise ValueError(f"fast_sample: the measurement of {degradation!r} is fp32 {list(shape)}; got {got}")
-            if sampling.check_resample(resample) > 1 and known_noise is None:
+            if resample > 1 and known_noise is None:
                 raise ValueError("fast_sample: resample > 1 needs `known_noise` (the key of the jumps' noise)")
         if inpaint:
             if known.dtype != torch.float32 or tuple(known.shape) != (B, D):
@@ -854,23 +834,14 @@ class _VDMBase:
             elif not hasattr(stepper, "set_context"):
                 raise TypeError("fast_sample: a re-used stepper must take the batch's context (set_context): "
                                 f"{type(stepper).__name__} cannot be re-targeted")
-            elif getattr(stepper, "step_eta", 0.0) != step_eta:
-                raise ValueError(f"fast_sample: the stepper's steps run with eta = {getattr(stepper, 'step_eta', 0.0)}, "
-                                 f"this run asks for {step_eta}")
-            elif bool(getattr(stepper, "inpaint", False)) != inpaint:
-                raise ValueError("fast_sample: the stepper was built %s a mask, this run comes %s one"
-                                 % (("without", "with") if inpaint else ("with", "without")))
-            elif getattr(stepper, "restore", None) != restore:
-                name = lambda r: "no degradation" if r is None else f"the degradation (f, gray) = {r}"
-                raise ValueError(f"fast_sample: the stepper was built for {name(getattr(stepper, 'restore', None))}, "
-                                 f"this run comes with {name(restore)}")
             else:
+                stepper.check_serves(step_eta, inpaint, restore)
                 stepper.set_context(ctx)
             if step_eta > 0.0:
                 stepper.set_noise(noise)
             if inpaint:
                 stepper.set_known(known, mask, known_noise)
-            if restoring:
+            if restore is not None:
                 stepper.set_measurement(measurement, known_noise)
             return sampling.run(stepper, z.reshape(B, D).contiguous(), grid, orders, resample)
 

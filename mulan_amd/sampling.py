@@ -20,15 +20,20 @@ ops.inpaint_mix, mulan_inpaint_mix).  The last mix (s = 0) takes zero noise, so 
 alpha_0 x and decode back to the input's integers.  With resample = U > 1 every step but the last is followed by U - 1
 rounds of: the forward transition q(z_t | z_s) back to t on fresh noise (ops.forward_jump, mulan_forward_jump), the step
 t -> s again at first order, and the mix; the history a repeated step leaves serves the next step as usual.
-The noise of the known region and of the jumps is known_noise_fn(j), j a counter of its own (run_inpaint states the law).
+The noise of the known region and of the jumps is known_noise_fn(j), j a counter of its own (run states the law).
 
 Restoration (range / null-space projection, DDNM): given a measurement y = A x of a degradation whose groups of
 sub-pixels A averages -- super-resolution 'sr:f', colourisation 'gray', or both -- the prediction x_hat of every step is
 replaced by x_hat' = x_hat + A+ (y - A x_hat) (ops.restore_project, mulan_restore_project) and the step runs on x_hat' as
 a data prediction (mode 2 of the same step kernels); the multistep history is x_hat'.  The projection lives in data
 space, so the different schedules inside a group do not enter.  resample = U > 1 is DDNM's time travel: U - 1 rounds of
-jump and first-order step after every step but the last (run_restore).
+jump and first-order step after every step but the last.
+
+One loop (run) and one step body (solver_step) serve the plain, the inpainting and the restoring run, for the stepper of
+this module and for the models' replayed one; check_guidance is the one place that decides which of the three a run is.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -171,6 +176,18 @@ def check_restore(sampler, measurement, degradation, resample=1, known=None, mas
     return True
 
 
+Guidance = collections.namedtuple("Guidance", "inpaint restore resample")
+
+
+def check_guidance(sampler, known=None, mask=None, measurement=None, degradation=None, resample=1):
+    """what guides a run, checked once for every layer that takes these keywords -> Guidance(inpaint: whether it
+    inpaints, restore: (f, gray) of a restoring run or None, resample: the passes per step as an int); raises what
+    check_restore and then check_inpaint raise"""
+    restoring = check_restore(sampler, measurement, degradation, resample, known, mask)
+    inpaint = check_inpaint(sampler, known, mask, 1 if restoring else resample)
+    return Guidance(inpaint, parse_degradation(degradation) if restoring else None, check_resample(resample))
+
+
 def mask_from_spec(spec):
     """a mask named in words -> bool [32, 32] (True = keep):
     'box:y0,x0,y1,x1'  the rows y0 .. y1 - 1 and columns x0 .. x1 - 1 are unknown, the rest is kept
@@ -225,21 +242,17 @@ class EagerStepper:
 
     def __init__(self, net_fn, gamma_fn, mode, step_eta=0.0, noise_fn=None, known=None, mask=None, known_noise_fn=None,
                  measurement=None, degradation=None, hwc=None):
-        self.net_fn, self.gamma_fn, self.mode = net_fn, gamma_fn, int(mode)
+        self.net_fn, self.gamma_fn, self.mode, self.hwc = net_fn, gamma_fn, int(mode), hwc
         self.step_eta, self.noise_fn = float(step_eta), noise_fn
         if self.step_eta > 0.0 and noise_fn is None:
             raise ValueError("a stochastic step (step_eta > 0) needs noise_fn(k) -> xi")
         self.g_prev = self.x_prev = None
         self._g = None              # (t, gamma(t)) of the last step's s: the next step's t
-        self.known = self.mask = self.known_noise_fn = None
+        self.known = self.mask = self.known_noise_fn = self.measurement = self.degradation = None
         restoring = measurement is not None or degradation is not None
         if known is not None or mask is not None or (known_noise_fn is not None and not restoring):
             self.set_known(known, mask, known_noise_fn)
-        self.measurement = self.degradation = None
-        self.hwc = hwc
         if restoring:
-            if self.inpaint:
-                raise ValueError("a mask and a measurement in one run are not supported: inpaint or restore")
             self.set_measurement(measurement, degradation, known_noise_fn)
 
     @property
@@ -251,6 +264,8 @@ class EagerStepper:
         return self.measurement is not None
 
     def set_measurement(self, measurement, degradation, known_noise_fn=None):
+        if self.inpaint:
+            raise ValueError("a mask and a measurement in one run are not supported: inpaint or restore")
         if measurement is None or degradation is None:
             raise ValueError("restoration needs the measurement and its degradation together")
         self.measurement, self.degradation = measurement, parse_degradation(degradation)
@@ -288,53 +303,60 @@ class EagerStepper:
         t, s = f32(t), f32(s)
         g_t = self._gamma(t)
         g_s = self.gamma_fn(s)
-        net, mode = self.net_fn(z, t), self.mode
-        if self.restore:
-            net = ops.restore_project(z, net, g_t, self.measurement, *self.degradation, mode, self.hwc)
-            mode = 2                # the step runs on x_hat', and its x0 output -- the history -- is x_hat' too
-        hist = (self.g_prev, self.x_prev) if order == 2 else (None, None)
+        net = self.net_fn(z, t)
         if order == 2 and self.g_prev is None:
             raise RuntimeError("a second-order step needs the history of a previous step")
-        if self.step_eta > 0.0:
-            if k is None:
-                raise ValueError("a stochastic step needs its index k (the noise is drawn per step)")
-            z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, mode, self.noise_fn(k), self.step_eta, *hist)
-        else:
-            z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, mode, *hist)
-        if mix is not None:
-            z_s = ops.inpaint_mix(z_s, self.known, self.mask, g_s, self._known_xi(mix), out=z_s)
-        self.g_prev, self.x_prev, self._g = g_t, x0, (s, g_s)
+        if self.step_eta > 0.0 and k is None:
+            raise ValueError("a stochastic step needs its index k (the noise is drawn per step)")
+        z_s, x0 = solver_step(z, net, g_t, g_s, self.mode, (self.g_prev, self.x_prev) if order == 2 else (None, None),
+                              (lambda: self.noise_fn(k)) if self.step_eta > 0.0 else None, self.step_eta, self.known,
+                              self.mask, (lambda: self._known_xi(mix)) if self.inpaint else None, self.measurement,
+                              self.degradation, self.hwc)
+        self.g_prev, self.x_prev, self._g = g_t, x0, (s, g_s)       # (a restoring step's x0, the history, is x_hat')
         return z_s
 
 
+def solver_step(z, net, g_t, g_s, mode, hist, xi=None, step_eta=0.0, known=None, mask=None, known_xi=None,
+                measurement=None, restore=None, hwc=None):
+    """the body of one step t -> s, behind the network: -> (z_s, x0).  restore = (f, gray) with its measurement: net is
+    projected onto the measurement first (ops.restore_project; hwc where z is not [B, H, W, C]) and the step runs on
+    x_hat' at mode 2, so x0 is x_hat'.  The step is ops.stochastic_sampler_step on the noise xi at step_eta where xi is
+    given, else ops.fast_sampler_step; hist = (g_prev, x_prev), or (None, None) at first order.  With a mask the known
+    sub-pixels of z_s are then replaced in place by alpha_s known + sigma_s known_xi (None: zero noise).  xi and known_xi
+    are tensors (static buffers, under graph capture) or thunks that draw them, called where the noise is needed."""
+    if restore is not None:
+        net, mode = ops.restore_project(z, net, g_t, measurement, *restore, mode, hwc), 2
+    if xi is not None:
+        z_s, x0 = ops.stochastic_sampler_step(z, net, g_t, g_s, mode, xi() if callable(xi) else xi, step_eta, *hist)
+    else:
+        z_s, x0 = ops.fast_sampler_step(z, net, g_t, g_s, mode, *hist)
+    if mask is not None:
+        z_s = ops.inpaint_mix(z_s, known, mask, g_s, known_xi() if callable(known_xi) else known_xi, out=z_s)
+    return z_s, x0
+
+
 def run(stepper, z, grid, orders, resample=1, known=None, mask=None, known_noise_fn=None):
-    """the solver loop: stepper(z, t, s, order, k) -> z_s along the grid; the step's index k selects the noise of a
-    stochastic step.  known / mask / known_noise_fn: handed to the stepper (set_known); a stepper that inpaints runs
-    run_inpaint with `resample`, one that restores (a measurement) run_restore"""
+    """the solver loop, the only one: stepper(z, t, s, order, k[, mix]) -> z_s along the grid; the step's index k selects
+    the noise of a stochastic step.  known / mask / known_noise_fn: handed to the stepper first (set_known).
+    An inpainting stepper (stepper.inpaint) has z_1 mixed at t = 1 (stepper.mix) and every step t -> s followed by the
+    mix at gamma_s, inside the stepper's call, which takes the `mix` argument: the draw j, or ZERO_NOISE at the last
+    step.  With resample = U > 1 an inpainting or a restoring stepper (stepper.restore: every step projects its
+    prediction onto the measurement) follows every step but the last with U - 1 rounds of jump s -> t (stepper.jump;
+    DDNM's time travel) and the step t -> s again at first order, with its mix where there is one.  Any other stepper
+    takes N plain steps, and resample != 1 is refused.
+    Noise: the known region's and the jumps' noise is draw j of the stepper's known_noise_fn, one counter for both.  A
+    deterministic run without resampling (step_eta = 0 and U = 1) uses j = 0 at every mix, so the known region follows
+    alpha_t x + sigma_t eps with one eps: a consistent trajectory for an ODE solver.  Otherwise every mix and every jump
+    takes the next j = 0, 1, 2, ... in the order they run (the mix of z_1 first; per round the jump, then the mix); a
+    restoring run has no mixes, so j counts its jumps, and with U = 1 it draws nothing.  Round r = 1 .. U - 1 of step k
+    draws the noise of its stochastic step under the step index k + r N (N steps), which no first pass uses."""
     assert len(orders) == len(grid) - 1
     if known is not None or mask is not None:
         stepper.set_known(known, mask, known_noise_fn)
-    if getattr(stepper, "inpaint", False):
-        return run_inpaint(stepper, z, grid, orders, resample)
-    if getattr(stepper, "restore", False):
-        return run_restore(stepper, z, grid, orders, resample)
-    if check_resample(resample) != 1:
-        raise ValueError("resample applies to inpainting (a known image and a mask) and to restoration (a measurement)")
-    for k, order in enumerate(orders):
-        z = stepper(z, grid[k], grid[k + 1], order, k)
-    return z
-
-
-def run_inpaint(stepper, z, grid, orders, resample=1):
-    """the solver loop of an inpainting stepper: z_1 mixed at t = 1; every step t -> s followed by the mix at gamma_s
-    (inside the stepper's call), the last one with zero noise; with resample = U > 1 every step but the last is followed
-    by U - 1 rounds of jump s -> t, the step t -> s again at first order, and the mix.
-    Noise: the known region's and the jumps' noise is the stepper's known_noise_fn(j).  A deterministic run (step_eta = 0
-    and U = 1) uses j = 0 at every mix, so the known region follows alpha_t x + sigma_t eps with one eps: a consistent
-    trajectory for an ODE solver.  Otherwise every mix and every jump takes the next j = 0, 1, 2, ... in the order they
-    run (the mix of z_1 first; per round the jump, then the mix).  Round r = 1 .. U - 1 of step k draws the noise of its
-    stochastic step under the step index k + r N (N steps), which no first pass uses."""
     U, N = check_resample(resample), len(orders)
+    inpaint = bool(getattr(stepper, "inpaint", False))
+    if U != 1 and not inpaint and not getattr(stepper, "restore", False):
+        raise ValueError("resample applies to inpainting (a known image and a mask) and to restoration (a measurement)")
     fresh = U > 1 or getattr(stepper, "step_eta", 0.0) > 0.0
     count = [0]
 
@@ -342,33 +364,15 @@ def run_inpaint(stepper, z, grid, orders, resample=1):
         j = count[0]
         count[0] += int(fresh)
         return j
-    z = stepper.mix(z, grid[0], draw())
+    if inpaint:
+        z = stepper.mix(z, grid[0], draw())
     for k, order in enumerate(orders):
         t, s, last = grid[k], grid[k + 1], k == N - 1
-        z = stepper(z, t, s, order, k, ZERO_NOISE if last else draw())
-        if not last:
-            for r in range(1, U):
+        for r in range(1 if last else U):
+            if r > 0:
                 z = stepper.jump(z, s, t, draw())
-                z = stepper(z, t, s, 1, k + r * N, draw())
-    return z
-
-
-def run_restore(stepper, z, grid, orders, resample=1):
-    """the solver loop of a restoring stepper (every step projects its prediction onto the measurement): run_inpaint
-    without the mixes.  With resample = U > 1 every step but the last is followed by U - 1 rounds of jump s -> t (DDNM's
-    time travel) and the step t -> s again at first order.  The jumps take known_noise_fn(j), j = 0, 1, 2, ... in the
-    order they run; a run with U = 1 draws nothing from it.  Round r = 1 .. U - 1 of step k draws the noise of its
-    stochastic step under the step index k + r N (N steps), as run_inpaint does."""
-    U, N = check_resample(resample), len(orders)
-    j = 0
-    for k, order in enumerate(orders):
-        t, s = grid[k], grid[k + 1]
-        z = stepper(z, t, s, order, k)
-        if k < N - 1:
-            for r in range(1, U):
-                z = stepper.jump(z, s, t, j)
-                j += 1
-                z = stepper(z, t, s, 1, k + r * N)
+            mix = (ZERO_NOISE if last else draw(),) if inpaint else ()
+            z = stepper(z, t, s, 1 if r > 0 else order, k + r * N, *mix)
     return z
 
 
@@ -378,14 +382,12 @@ def sample(net_fn, gamma_fn, z, mode, sampler="dpm2m", steps=None, t_grid=None, 
     ops.fast_sampler_step (0: net_fn gives the velocity, 1: eps_hat, 2: x_hat).  eta (ddim only): 0 is the
     deterministic sampler; sde2m and ddim with eta > 0 need noise_fn(k) -> xi shaped like z, the noise of step k.
     known, mask (shaped like z: the image as ops.encode_u8 gives it, one byte per element, non-zero = keep): inpainting
-    with `resample` passes per step, on known_noise_fn(j) -> xi shaped like z (run_inpaint states which j is drawn
-    when).
+    with `resample` passes per step, on known_noise_fn(j) -> xi shaped like z (run states which j is drawn when).
     measurement, degradation (a spec of parse_degradation, or its pair): restoration instead, the measurement fp32
     shaped ops.restore_y_shape in the scale of ops.encode_u8; z is [B, H, W, C] or hwc names (H, W, C); `resample`
-    passes per step on known_noise_fn(j), the noise of jump j (run_restore)"""
+    passes per step on known_noise_fn(j), the noise of jump j (run)"""
     step_eta = check_eta(sampler, eta)
-    restore = check_restore(sampler, measurement, degradation, resample, known, mask)
-    check_inpaint(sampler, known, mask, 1 if restore else resample)
+    check_guidance(sampler, known, mask, measurement, degradation, resample)
     grid = time_grid(steps, t_grid)
     orders = step_orders(sampler, len(grid) - 1)
     with torch.no_grad():

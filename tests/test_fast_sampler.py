@@ -71,6 +71,48 @@ def test_order_schedule():
         sampling.check_sampler("dpm3")
 
 
+@pytest.mark.parametrize("sampler,N", [("dpm2m", 4), ("ddim", 3), ("dpm2m", 16), ("sde2m", 1)])
+def test_run_asks_a_plain_stepper_for_the_steps_of_the_schedule(sampler, N):
+    """sampling.run driven with a recording stepper that neither inpaints nor restores: N steps under the indices
+    0 .. N - 1 at the schedule's orders, no mix and no jump; resample = 2 is refused"""
+    import torch
+    from mulan_amd import sampling
+    from tests.test_inpaint import _Recorder
+    f32 = lambda v: float(np.float32(v))
+    grid, orders = sampling.time_grid(N), sampling.step_orders(sampler, N)
+    rec = _Recorder(sampling.check_eta(sampler), inpaint=False, restore=False)
+    z = torch.zeros(1, 4)
+    assert sampling.run(rec, z, grid, orders) is z
+    assert rec.log == [("step", orders[k], k, None, f32(grid[k]), f32(grid[k + 1])) for k in range(N)]
+    with pytest.raises(ValueError, match=re.escape("resample applies to inpainting (a known image and a mask) and to "
+                                                   "restoration (a measurement)")):
+        sampling.run(rec, z, grid, orders, 2)
+    assert len(rec.log) == N                                  # refused before any step
+
+
+def test_a_stepper_refuses_the_runs_it_was_not_built_for():
+    """the three refusals of a re-used stepper in fast_sample, on eager steppers built on the CPU (no launch)"""
+    import types
+    from mulan_amd import model as M
+    build = lambda **kw: M.EagerFastStep(types.SimpleNamespace(_fast_mode=lambda: 1), None, 2, "cpu", {}, **kw)
+    plain, sde, masked, sr4 = build(), build(step_eta=1.0), build(inpaint=True), build(restore="sr:4")
+    assert plain.check_serves(0.0, False, None) is None and sde.check_serves(1.0, False, None) is None
+    assert masked.check_serves(0.0, True, None) is None and sr4.check_serves(0.0, False, (4, False)) is None
+    for stepper, args, text in (
+            (plain, (1.0, False, None), "fast_sample: the stepper's steps run with eta = 0.0, this run asks for 1.0"),
+            (sde, (0.5, True, None), "fast_sample: the stepper's steps run with eta = 1.0, this run asks for 0.5"),
+            (plain, (0.0, True, None), "fast_sample: the stepper was built without a mask, this run comes with one"),
+            (masked, (0.0, False, None), "fast_sample: the stepper was built with a mask, this run comes without one"),
+            (plain, (0.0, False, (4, False)), "fast_sample: the stepper was built for no degradation, this run comes with "
+                                              "the degradation (f, gray) = (4, False)"),
+            (sr4, (0.0, False, (2, True)), "fast_sample: the stepper was built for the degradation (f, gray) = (4, False), "
+                                           "this run comes with the degradation (f, gray) = (2, True)"),
+            (sr4, (0.0, False, None), "fast_sample: the stepper was built for the degradation (f, gray) = (4, False), this "
+                                      "run comes with no degradation")):
+        with pytest.raises(ValueError, match="^" + re.escape(text) + "$"):
+            stepper.check_serves(*args)
+
+
 def _base_args(tmp_path):
     return [f"--config={CONFIG}", f"--checkpoint_directory={tmp_path}", "--n_samples=4", f"--out={tmp_path}/s.npz"]
 

@@ -1,4 +1,4 @@
-"""Inpainting with the few-step samplers (mulan_amd.sampling.run_inpaint): the two HIP kernels against float64
+"""Inpainting with the few-step samplers (mulan_amd.sampling.run): the two HIP kernels against float64
 (tests/inpaint_oracle.py), their exact cases, ragged sizes and refusals, the law of the jump and of the whole loop on a
 linear-Gaussian model, the whole models against the float64 oracle loop on shared noise, the replayed stepper against the
 eager one, the notebook front end and the `python -m ldm.sample` CLI."""
@@ -391,7 +391,7 @@ def test_inpainting_matches_the_oracle_loop(vdm_type, unet_type, vfe):
 def test_inpainting_runs_match_the_oracle_loop(vdm_type, unet_type, vfe):
     """the product's own loop: fast_sample with a mask on the shared noise (callables k -> xi, j -> xi), eager and
     replayed, run free from z_1 against the z_0 of the oracle's loop, for dpm2m at resample 1 (4 network evaluations)
-    and sde2m at resample 2 (7).  This holds what run_inpaint decides -- which draw goes where, one eps throughout the
+    and sde2m at resample 2 (7).  This holds what sampling.run decides -- which draw goes where, one eps throughout the
     deterministic run, first order and the step index k + r N on a repeated step, the history it leaves -- to the
     oracle's restatement.  On the damped network of test_fast_samplers_match_the_oracle's free run, with its bar taken
     over every network evaluation of the run, the repeated ones included: 4 x (2e-4 of the summed step budgets + the

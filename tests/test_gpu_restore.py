@@ -1,4 +1,4 @@
-"""Restoration with the few-step samplers (mulan_amd.sampling.run_restore): the projection and measurement kernels
+"""Restoration with the few-step samplers (mulan_amd.sampling.run): the projection and measurement kernels
 against float64 (tests/restore_oracle.py) on every degradation and group size, their refusals, the restoring step as
 projection + the existing step kernel bit for bit, the whole models against the float64 oracle loop on shared noise, the
 replayed stepper against the eager one, the front ends and the law A z_0 = k_z A z_t + k_x y on a linear-Gaussian model."""

@@ -1,4 +1,4 @@
-"""Inpainting with the few-step samplers (mulan_amd.sampling.run_inpaint): the two C ABI entry points, the masks, the
+"""Inpainting with the few-step samplers (mulan_amd.sampling.run): the two C ABI entry points, the masks, the
 refusals, the flags of `python -m ldm.sample` and the float64 oracle (tests/inpaint_oracle.py) against its known
 answers -- everything that runs without a GPU."""
 import os
@@ -113,7 +113,7 @@ def test_gaussian_law_with_resampling_keeps_the_exact_marginal_mean():
 
 
 def test_oracle_loop_order_of_operations():
-    """the loop on a toy model: the events, their step indices and noise draws are those run_inpaint states"""
+    """the loop on a toy model: the events, their step indices and noise draws are those sampling.run states"""
     B, n, N = 1, 4, 3
     d = torch.float64
     gamma = lambda t: torch.full((B, 1), -13.3 + 18.3 * t, dtype=d)
@@ -135,10 +135,11 @@ def test_oracle_loop_order_of_operations():
 
 
 class _Recorder:
-    """a stepper that computes nothing and writes down what the loop asks of it"""
+    """a stepper that computes nothing and writes down what the loop asks of it (tests/test_restore.py and
+    tests/test_fast_sampler.py drive it as a restoring and as a plain stepper)"""
 
-    def __init__(self, step_eta):
-        self.step_eta, self.inpaint, self.log = step_eta, True, []
+    def __init__(self, step_eta, inpaint=True, restore=False):
+        self.step_eta, self.inpaint, self.restore, self.log = step_eta, inpaint, restore, []
 
     def mix(self, z, t, j):
         self.log.append(("mix", None, None, j, float(np.float32(t)), None))
@@ -156,7 +157,7 @@ class _Recorder:
 @pytest.mark.parametrize("sampler,eta,U,N", [("dpm2m", 0.0, 1, 4), ("sde2m", 1.0, 2, 4), ("sde2m", 1.0, 3, 16),
                                              ("ddim", 0.0, 2, 3), ("ddim", 0.5, 1, 3), ("dpm2m", 0.0, 2, 15)])
 def test_run_inpaint_asks_for_what_the_oracle_loop_does(sampler, eta, U, N):
-    """sampling.run_inpaint driven with a recording stepper: the sequence of operations with their order, step index,
+    """sampling.run driven with a recording stepper: the sequence of operations with their order, step index,
     noise draw and times equals the events of the oracle's loop -- one eps (j = 0) throughout the deterministic run,
     consecutive draws otherwise, first order and the index k + r N on a repeated step, zero noise at the last mix"""
     from mulan_amd import sampling

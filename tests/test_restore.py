@@ -1,4 +1,4 @@
-"""Restoration with the few-step samplers (mulan_amd.sampling.run_restore): the degradation grammar, the refusals, the
+"""Restoration with the few-step samplers (mulan_amd.sampling.run): the degradation grammar, the refusals, the
 two C ABI entry points in the header and the binding table, the flags of `python -m ldm.sample` and the float64 oracle
 (tests/restore_oracle.py) against its known answers -- everything that runs without a GPU."""
 import os
@@ -249,3 +249,78 @@ def test_sample_cli_refusals(tmp_path):
             ([], "n_samples")):
         with pytest.raises(SystemExit, match=match):
             sample.parse_flags(base + args)
+
+
+# ------------------------------------------------------------------------------------- the loop and the one check
+@pytest.mark.parametrize("sampler,eta,U,N", [("dpm2m", 0.0, 1, 4), ("sde2m", 1.0, 2, 4), ("ddim", 0.5, 3, 3),
+                                             ("dpm2m", 0.0, 2, 15)])
+def test_run_asks_a_restoring_stepper_for_steps_and_jumps_only(sampler, eta, U, N):
+    """sampling.run driven with a recording stepper that restores: step k at the schedule's order and no `mix`; after
+    every step but the last, rounds r = 1 .. U - 1 of a jump s -> t on j = 0, 1, 2, ... counted over the whole run,
+    then the step again at first order under the index k + r N; U = 1 draws no j at all"""
+    from mulan_amd import sampling
+    from tests.test_inpaint import _Recorder
+    f32 = lambda v: float(np.float32(v))
+    grid, orders = sampling.time_grid(N), sampling.step_orders(sampler, N)
+    want, j = [], 0
+    for k in range(N):
+        t, s = f32(grid[k]), f32(grid[k + 1])
+        want.append(("step", orders[k], k, None, t, s))
+        for r in range(1, U if k < N - 1 else 1):
+            want += [("jump", None, None, j, t, s), ("step", 1, k + r * N, None, t, s)]
+            j += 1
+    rec = _Recorder(sampling.check_eta(sampler, eta if sampler == "ddim" else 0.0), inpaint=False, restore=True)
+    z = torch.zeros(1, 4)
+    assert sampling.run(rec, z, grid, orders, U) is z
+    assert rec.log == want
+    steps, jumps = ([e for e in rec.log if e[0] == kind] for kind in ("step", "jump"))
+    assert len(steps) == N + (U - 1) * (N - 1) and len(jumps) == (U - 1) * (N - 1)
+    assert [e[3] for e in jumps] == list(range(len(jumps))) and not any(e[0] == "mix" for e in rec.log)
+
+
+def _guidance_on_the_parent(sampler, known, mask, measurement, degradation, resample):
+    """the three public checks in the order every layer used to spell out -> (inpaint, restore, resample)"""
+    from mulan_amd import sampling
+    restoring = sampling.check_restore(sampler, measurement, degradation, resample, known, mask)
+    inpaint = sampling.check_inpaint(sampler, known, mask, 1 if restoring else resample)
+    return inpaint, sampling.parse_degradation(degradation) if restoring else None, sampling.check_resample(resample)
+
+
+_X, _M, _Y = torch.zeros(1, 4), torch.ones(1, 4, dtype=torch.uint8), torch.zeros(1, 2, 2, 3)
+
+
+@pytest.mark.parametrize("sampler,known,mask,measurement,degradation,resample", [
+    ("dpm2m", None, None, None, None, 1),                     # nothing given
+    ("ancestral", None, None, None, None, 1),
+    ("dpm3", None, None, None, None, 1),                      # no such sampler
+    ("dpm2m", _X, _M, None, None, 1), ("sde2m", _X, _M, None, None, 3),
+    ("dpm2m", None, None, _Y, "sr:4", 1), ("ddim", None, None, _Y, (2, True), 2), ("sde2m", None, None, _Y, "gray", 1),
+    ("dpm2m", None, _M, None, None, 1), ("dpm2m", _X, None, None, None, 1),           # one without the other
+    ("dpm2m", None, None, _Y, None, 1), ("dpm2m", None, None, None, "sr:4", 1),
+    ("dpm2m", _X, _M, _Y, "sr:4", 1), ("dpm2m", None, _M, _Y, "sr:4", 2),             # both kinds at once
+    ("dpm2m", _X, _M, None, "sr:4", 1), ("dpm2m", _X, _M, _Y, None, 1),
+    ("ancestral", _X, _M, None, None, 1), ("ancestral", None, None, _Y, "sr:4", 1),
+    ("ancestral", _X, _M, _Y, "sr:4", 1),
+    ("dpm2m", None, None, None, None, 0), ("dpm2m", None, None, None, None, 1.5), ("dpm2m", None, None, None, None, True),
+    ("dpm2m", None, None, None, None, None), ("dpm2m", None, None, None, None, 2),    # resample without guidance
+    ("dpm2m", _X, _M, None, None, 0), ("dpm2m", None, None, _Y, "sr:4", 1.5), ("dpm2m", None, None, _Y, "sr:4", None),
+    ("dpm2m", _X, _M, None, None, 2.0),
+    ("dpm2m", None, None, _Y, "sr:3", 1), ("dpm2m", None, None, _Y, "gray+sr:2", 2), ("dpm2m", None, None, _Y, (1, False), 1),
+    ("dpm2m", _X, _M, _Y, "sr:3", 1)])                        # a malformed degradation
+def test_check_guidance_is_the_three_checks_in_their_order(sampler, known, mask, measurement, degradation, resample):
+    """check_guidance returns what check_restore, check_inpaint and parse_degradation decide, or raises the first
+    error that sequence raises: the same type and the same text"""
+    from mulan_amd import sampling
+    args = (sampler, known, mask, measurement, degradation, resample)
+    try:
+        want = _guidance_on_the_parent(*args)
+    except (ValueError, TypeError) as e:
+        with pytest.raises(type(e)) as got:
+            sampling.check_guidance(*args)
+        assert type(got.value) is type(e) and str(got.value) == str(e)
+        return
+    got = sampling.check_guidance(*args)
+    assert tuple(got) == want and (got.inpaint, got.restore, got.resample) == want
+    assert type(got.resample) is int and type(got.inpaint) is bool
+    with pytest.raises(AttributeError):
+        got.resample = 7                                      # the record is immutable

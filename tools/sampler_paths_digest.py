@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""dev: SHA-256 of what every way of running a trained model computes -- the ancestral sampler, the few-step samplers,
-one probability-flow ODE function evaluation and decoding, eager and as replayed HIP graphs -- for each model flavour at
-B = 2, E = 128, one layer, fixed seeds and random weights.  It calls public names of mulan_amd.model only, so the same
+"""dev: SHA-256 of what every way of running a trained model computes -- the ancestral sampler, the few-step samplers
+(plain, stochastic, inpainting and restoring, with and without resampling), one probability-flow ODE function evaluation
+and decoding, eager and as replayed HIP graphs -- for each model flavour at B = 2, E = 128, one layer, fixed seeds and
+random weights.  It calls public names of mulan_amd.model only, so the same
 file runs before and after a change of the host code that drives these kernels: record both and compare the two files
 (see profiles/README.md); equal digests mean equal bits.
     python tools/sampler_paths_digest.py --out digests.log
@@ -16,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from mulan_amd import lib, ops
+from mulan_amd import lib, ops, sampling
 from mulan_amd import model as M
 from mulan_amd.rng import PRNGKey
 
@@ -89,6 +90,25 @@ def _paths(name, vdm_type, fields):
                 stepper = model.fast_stepper(params, B, dev, ctx, graph=graph)
                 z = model.fast_sample(params, z1.clone(), ctx, sampler, 4, stepper=stepper)
                 _digest(f"{sampler}, 4 steps, {'replayed' if graph else 'eager'}", z, by=type(stepper).__name__)
+        # the guided and the stochastic runs: a half:left mask and an sr:2+gray measurement of one seeded image
+        image = torch.randint(0, 256, (B, 32, 32, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(17)).cuda()
+        masked = dict(known=ops.encode_u8(image).reshape(B, 3072), known_noise=PRNGKey(19),
+                      mask=sampling.expand_mask(sampling.mask_from_spec("half:left"), B, dev))
+        measured = dict(measurement=ops.restore_measure(ops.encode_u8(image), 2, True), degradation="sr:2+gray",
+                        known_noise=PRNGKey(19))
+        runs = [("sde2m", 0.0, "", {}), ("ddim", 0.5, " eta = 0.5", {})]
+        runs += [(sm, 0.0, f" under half:left, resample {U}", dict(masked, resample=U))
+                 for sm, U in (("dpm2m", 1), ("dpm2m", 2), ("sde2m", 2))]
+        runs += [(sm, 0.0, f" under sr:2+gray, resample {U}", dict(measured, resample=U))
+                 for sm in ("dpm2m", "sde2m") for U in (1, 2)]
+        for sampler, eta, what, kw in runs:
+            step_eta = sampling.check_eta(sampler, eta)
+            for graph in (False, True):
+                stepper = model.fast_stepper(params, B, dev, ctx, graph=graph, step_eta=step_eta, inpaint="mask" in kw,
+                                             restore=kw.get("degradation"))
+                z = model.fast_sample(params, z1.clone(), ctx, sampler, 4, stepper=stepper, eta=eta,
+                                      noise=PRNGKey(18) if step_eta > 0.0 else None, **kw)
+                _digest(f"{sampler}{what}, 4 steps, {'replayed' if graph else 'eager'}", z, by=type(stepper).__name__)
         z0 = PRNGKey(13).normal((B, 3072), dev)
         _digest("generate_x, argmax", model.generate_x(params, z0, coeffs))
         softmax = M.make_vdm(vdm_type, dataclasses.replace(cfg, sample_softmax=True))
