@@ -227,15 +227,17 @@ int mulan_param_pack_f16x3(const float* flat, const long long* leaves, int n, co
  * (model_vdm.py:676-685).  Rows are pixels (rows_per_img per image); x1max / x2max are per-image maxima in the
  * mulan_absmax_rows format; wp from mulan_linear_pack_f16x3 (transpose = 1 packs w^T for dx = dy @ w^T);
  * wmax[16] = mulan_absmax_rows(w, 1 row).  Needs M % 128 == 0, rows_per_img % 128 == 0, K1, K2 % 32 == 0,
- * N1, N2 % 128 == 0 (K2 = 0 / N2 = 0 without x2 / y2); res only with N2 = 0. */
+ * N1, N2 % 128 == 0 (K2 = 0 / N2 = 0 without x2 / y2); res only with N2 = 0.  The pack calls need K % 16 == 0 (any
+ * N) and a non-null wmax.  A call that breaks one of these returns non-zero before any launch and writes nothing.
+ * (tests/test_gpu_linear_f16x3.py) */
 size_t mulan_linear_pack_f16x3_bytes(int K, int N);
 int mulan_linear_pack_f16x3(const float* w, void* wp, const unsigned* wmax, int K, int N, int transpose,
                             mulan_stream_t stream);
 int mulan_linear_f16x3(const float* x1, const unsigned* x1max, const float* x2, const unsigned* x2max, int K1, int K2,
                        const void* wp, const unsigned* wmax, const float* bias, const float* res, float* y1, float* y2,
                        void* xs, int N1, int N2, int M, int rows_per_img, mulan_stream_t stream);
-/* xs (optional, M (K1+K2) 4 bytes): the layer hands the split planes of [x1 | x2] on (scaled per image with the larger
- * of the two maxima).  Its weight gradient dw[K1+K2, N] (+)= [x1|x2]^T dy then comes from those planes and the planes of
+/* xs (optional, M (K1+K2) 4 bytes, below 2 GiB): the layer hands the split planes of [x1 | x2] on (scaled per image with
+ * the larger of the two maxima).  Its weight gradient dw[K1+K2, N] (+)= [x1|x2]^T dy then comes from those planes and the planes of
  * dy handed on by the convolution that consumed the same dy (nin_shortcut and conv2 of a ResnetBlock share dy):
  * H x W = 32 x 32 pixels per image; C = K1 + K2 and N multiples of 128; xmax = elementwise max of x1max, x2max. */
 size_t mulan_linear_wgrad_f16x3_planes_workspace(int B, int H, int W, int C, int N, int share_chip);
@@ -254,7 +256,7 @@ int mulan_linear_wgrad_f16x3_x32(const float* x1, const float* x2, int C1, int C
                                  mulan_stream_t stream);
 /* The attention products (lax.dot_general in dot_product_attention, model_vdm.py:775-796, and their autodiff) on the
  * same kernels, one operand per image:  y[b] = x[b] @ W[b] (+ res) with W[b] packed by the batched pack (w: batch
- * operands [K, N], or [N, K] with transpose = 1; wmax [batch][16] = mulan_absmax_rows(w, batch rows)) at
+ * operands [K, N], or [N, K] with transpose = 1, 1 <= batch <= 65535; wmax [batch][16] = mulan_absmax_rows(w, batch rows)) at
  * wp + b * K * N * 4 bytes;  out[b] = x[b]^T @ dy[b] ([C, N] per image) from the planes the forward products hand on
  * (S = Q K^T, O = P V, dP = dO V^T, dQ = dS K by the first form; dV = P^T dO, dK = dS^T Q by the second). */
 int mulan_linear_pack_f16x3_batched(const float* w, void* wp, const unsigned* wmax, int K, int N, int transpose,

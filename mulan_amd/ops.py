@@ -1615,13 +1615,14 @@ def _pack_batched(w, transpose, wmax):
     return wp
 
 
-def linear_batched_raw(x, xmax, wp, wmax, N, planes=False):
-    """y[b] = x[b] @ W[b]: x [B, 1024, K]; returns y [B, 1024, N] (+ the split planes of x when planes=True)"""
+def linear_batched_raw(x, xmax, wp, wmax, N, planes=False, res=None):
+    """y[b] = x[b] @ W[b] (+ res [B, 1024, N]): x [B, 1024, K]; returns y [B, 1024, N] (+ the split planes of x when
+    planes=True)"""
     B, R, K = x.shape
     y = torch.empty((B, R, N), device=x.device, dtype=torch.float32)
     xs = torch.empty(B * R * K * 4, device=x.device, dtype=torch.uint8) if planes else None
     _timed("linear_f16x3_kernel(batched)", 2.0 * B * R * K * N,
-           lambda: call("mulan_linear_f16x3_batched", ptr(x), ptr(xmax), K, ptr(wp), ptr(wmax), None, ptr(y), ptr(xs), N,
+           lambda: call("mulan_linear_f16x3_batched", ptr(x), ptr(xmax), K, ptr(wp), ptr(wmax), ptr(res), ptr(y), ptr(xs), N,
                         B * R, R, stream()))
     return (y, xs) if planes else y
 

@@ -260,6 +260,7 @@ def test_f16x3_plane_fed_wgrad(ops, B, C, N, ints):
         assert e_p < 1e-5 and e_p < 2 * e_9 + 1e-6, (e_p, e_9)
 
 
+# (the tiles, scales and edges of this kernel family off the model's shapes: tests/test_gpu_linear_f16x3.py)
 @pytest.mark.parametrize("B,K1,K2,N", [(2, 128, 0, 128), (1, 128, 128, 128), (3, 256, 0, 256), (2, 128, 128, 256)])
 def test_f16x3_linear_exact_on_integers_and_accuracy(ops, B, K1, K2, N):
     """[x1 | x2] @ w + bias + res through the f16x3 per-pixel dense kernel, and dy @ w^T split into two outputs"""
@@ -300,6 +301,7 @@ def test_f16x3_linear_exact_on_integers_and_accuracy(ops, B, K1, K2, N):
                 assert float((np.abs(got_dx[b] - dxr[b]) / magd).max()) < 2e-6, b
 
 
+# (the tiles, scales and edges of this kernel family off the model's shapes: tests/test_gpu_linear_f16x3.py)
 @pytest.mark.parametrize("B,K1,K2,N", [(3, 128, 128, 128), (2, 256, 0, 256), (5, 128, 0, 128)])
 def test_f16x3_linear_row_tile_variants_are_bit_identical(ops, B, K1, K2, N):
     """64-row blocks (round 5: launches with fewer 128-row blocks than CUs -- a 16-image sampling batch) against 128-row
@@ -636,6 +638,7 @@ def test_gn_backward_sums_over_samples_inside_the_launch(ops, monkeypatch, B, C2
     assert int(ops._gn_tickets(x.device).abs().sum()) == 0
 
 
+# (the tiles, scales and edges of this kernel family off the model's shapes: tests/test_gpu_linear_f16x3.py)
 @pytest.mark.parametrize("B,K1,K2,N", [(2, 128, 128, 128), (3, 128, 0, 128), (1, 256, 256, 256)])
 def test_f16x3_dense_weight_gradient_from_planes(ops, B, K1, K2, N):
     """dw = [x1|x2]^T dy of a per-pixel dense layer from the planes handed on by its forward kernel and by the
@@ -675,6 +678,7 @@ def test_f16x3_dense_weight_gradient_from_planes(ops, B, K1, K2, N):
 
 
 # ------------------------------------------------------------------------------------------------ attention products
+# (the tiles, scales and edges of this kernel family off the model's shapes: tests/test_gpu_linear_f16x3.py)
 @pytest.mark.parametrize("B,K,N,transpose", [(3, 128, 1024, True), (2, 1024, 128, False), (2, 256, 1024, True)])
 def test_f16x3_batched_linear_exact_on_integers(ops, B, K, N, transpose):
     """y[b] = x[b] @ W[b] with one packed operand and one scale per image (the attention products): bit-exact on
