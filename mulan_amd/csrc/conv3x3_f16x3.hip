@@ -810,39 +810,7 @@ struct WgradArgsP {
   // and is split while it is staged; xmax holds the maxima of the concat (elementwise max of the two tensors' maxima)
   const float* x1f; const float* x2f; int C1;
   const unsigned* xmax2;                               // (XF32) maxima of x2: the concat's are the elementwise max of xmax, xmax2
-  // (w16 kernel, mulan_conv3x3_wgrad_f16x3_planes_fold) slab reductions of EARLIER launches that this launch's blocks
-  // perform in their prologue, while their first operand loads are in flight
-  mulan_slab_reduction pend[2];
-  int npend;
 };
-
-// out[e] (+)= sum over the S slabs, in slab order (the order -- and therefore the bits -- of slab_reduce_h_kernel), four
-// outputs per thread; gtid / gthreads: this thread's index in / the size of the whole launch.  Up to 16 loads in flight.
-__device__ __forceinline__ void fold_slab_reduction(const mulan_slab_reduction& r, int gtid, int gthreads) {
-  const int E4 = r.E >> 2;
-  for (int e = gtid; e < E4; e += gthreads) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(r.slab) + e;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    int i = 0;
-    for (; i + 16 <= r.S; i += 16) {
-      f32x4 v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = src[(size_t)(i + u) * E4];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) s += v[u];
-    }
-    for (; i + 4 <= r.S; i += 4) {
-      f32x4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = src[(size_t)(i + u) * E4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s += v[u];
-    }
-    for (; i < r.S; ++i) s += src[(size_t)i * E4];
-    f32x4* o = reinterpret_cast<f32x4*>(r.out) + e;
-    *o = r.accumulate ? *o + s : s;
-  }
-}
 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -853,28 +821,23 @@ __device__ __forceinline__ int clamped_exp(unsigned maxbits) {
 }
 
 
-// The four-wave block: a wave owns 64 ci x 64 co x TAPS on v_mfma_f32_32x32x16_f16.
-// TAPS = 1 (the only form instantiated): a 1x1 "convolution", i.e. the weight gradient x^T dy of a per-pixel dense layer
-// (nin_shortcut, the attention projections and the attention core's batched products) from the planes its forward
-// kernel handed on: only the centre tap of the LDS image.  TAPS = 3: one kernel row of a 3x3 convolution per block
-// (blockIdx.y = kh), the form the eight-wave kernel below replaced (retired; kept in the source only because dropping
-// the parameter reorders the operands of one instruction of the shipped one-tap code, see DESIGN.md section 3.2: to be
-// dropped with the three-tap code the next time this kernel's code changes anyway).
-// XF32 (TAPS = 1): the x operand is read in fp32 and split in the staging path instead of arriving as planes.  The
+// The four-wave block, one tap: a wave owns 64 ci x 64 co on v_mfma_f32_32x32x16_f16.  A 1x1 "convolution", i.e. the
+// weight gradient x^T dy of a per-pixel dense layer (nin_shortcut, the attention projections and the attention core's
+// batched products) from the planes its forward kernel handed on: only the centre tap of the LDS image (the haloed x
+// row layout is the one the eight-wave 3x3 kernel below shares; the halo columns are staged and never read).
+// XF32: the x operand is read in fp32 and split in the staging path instead of arriving as planes.  The
 // dense weight gradient is memory bound (48 MFMAs per wave and row pair against 68 KB of operands), so the split
 // arithmetic is free there, and the layer's forward kernel no longer has to write the planes of its input (134 MB per
 // nin_shortcut at E = 128: 27 us of a 83 us launch, profiles/r03_linear_probe.log).  Same values as the planes the
 // forward kernel used to hand on (split2 of x * s with the concat's per-image scale): bit-identical dw.
-template <int TAPS, bool XF32 = false>
+template <bool XF32 = false>
 __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradArgsP p) {
-  static_assert(!XF32 || TAPS == 1, "fp32 x operand: one-tap kernel only");
-  constexpr int NQ = 4 * TAPS;                   // stages per row pair: 4 k steps x TAPS
+  constexpr int NQ = 4;                          // stages per row pair: 4 k steps
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int wci = wave >> 1, wco = wave & 1;
   const int C = p.C, N = p.N;
-  const int kh = TAPS == 3 ? blockIdx.y : 1;
   const int ntn = N / WG3_T;
   const int c0 = (blockIdx.z / ntn) * WG3_T, n0 = (blockIdx.z % ntn) * WG3_T;
   const int nchc = C / 16, nchn = N / 16;
@@ -888,15 +851,13 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
   const int pair_begin = (int)((long long)blockIdx.x * total_pairs / p.S);
   const int pair_end = (int)((long long)(blockIdx.x + 1) * total_pairs / p.S);
 
-  f32x16 acc[TAPS][2][2];   // [kw][ci tile][co tile]
+  f32x16 acc[2][2];         // [ci tile][co tile]
 #pragma unroll
-  for (int t = 0; t < TAPS; ++t)
+  for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][i][j][r] = 0.f;
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   // staging units of 16 bytes (8 channels of one plane of one pixel): unit e = tid + 256 i,
   //   e & 3 -> (plane, channel half),  e >> 2 = chunk * pixels + pixel   (consecutive lanes: consecutive 64-B records)
@@ -929,7 +890,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
     const int t = (tid >> 2) + 64 * i;
     const int cc = t / X3PIX, pix = t - cc * X3PIX;
     const int prow = pix / kPW, pcol = pix - prow * kPW;
-    const int hh = h0 + kh - 1 + prow;
+    const int hh = h0 + prow;
     const bool ok = t < 8 * X3PIX && pcol >= 1 && pcol <= kW && hh >= 0 && hh < p.H;
     const unsigned off = (unsigned)((((b * nchc + (c0 >> 4) + cc) * 1024 + hh * kW + pcol - 1) * 2 + upl) * 32 + uh * 16);
     xreg[i] = __builtin_amdgcn_raw_buffer_load_b128(xs_rsrc, ok ? off : 0xffffffffu, 0, 0);
@@ -1029,25 +990,23 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
       // Neighbouring images mostly share their exponents: nothing to do then.
       if (d != 0) {
 #pragma unroll
-      for (int t = 0; t < TAPS; ++t)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; r += 4) {
-              float t0, t1, t2, t3;
-              asm volatile(
-                  "v_accvgpr_read_b32 %4, %0\n\tv_accvgpr_read_b32 %5, %1\n\t"
-                  "v_accvgpr_read_b32 %6, %2\n\tv_accvgpr_read_b32 %7, %3\n\ts_nop 0\n\t"
-                  "v_ldexp_f32 %4, %4, %8\n\tv_ldexp_f32 %5, %5, %8\n\tv_ldexp_f32 %6, %6, %8\n\tv_ldexp_f32 %7, %7, %8\n\t"
-                  "s_nop 1\n\t"
-                  "v_accvgpr_write_b32 %0, %4\n\tv_accvgpr_write_b32 %1, %5\n\t"
-                  "v_accvgpr_write_b32 %2, %6\n\tv_accvgpr_write_b32 %3, %7"
-                  : "+a"(acc[t][i][j][r]), "+a"(acc[t][i][j][r + 1]), "+a"(acc[t][i][j][r + 2]), "+a"(acc[t][i][j][r + 3]),
-                    "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
-                  : "v"(d));
-            }
+          for (int r = 0; r < 16; r += 4) {
+            float t0, t1, t2, t3;
+            asm volatile(
+                "v_accvgpr_read_b32 %4, %0\n\tv_accvgpr_read_b32 %5, %1\n\t"
+                "v_accvgpr_read_b32 %6, %2\n\tv_accvgpr_read_b32 %7, %3\n\ts_nop 0\n\t"
+                "v_ldexp_f32 %4, %4, %8\n\tv_ldexp_f32 %5, %5, %8\n\tv_ldexp_f32 %6, %6, %8\n\tv_ldexp_f32 %7, %7, %8\n\t"
+                "s_nop 1\n\t"
+                "v_accvgpr_write_b32 %0, %4\n\tv_accvgpr_write_b32 %1, %5\n\t"
+                "v_accvgpr_write_b32 %2, %6\n\tv_accvgpr_write_b32 %3, %7"
+                : "+a"(acc[i][j][r]), "+a"(acc[i][j][r + 1]), "+a"(acc[i][j][r + 2]), "+a"(acc[i][j][r + 3]),
+                  "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
+                : "v"(d));
+          }
       }
       b_acc = b_now;
     }
@@ -1061,20 +1020,19 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) af[0][i][pl] = tr_read8h(xa + pl * X3_PLANE + i * X3_HALF + (TAPS == 1 ? 64 : 0));
+      for (int pl = 0; pl < 2; ++pl) af[0][i][pl] = tr_read8h(xa + pl * X3_PLANE + i * X3_HALF + 64);
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {                     // q = ks * TAPS + tap; k step ks = 16 pixels of row rr = ks >> 1
-      const int ks = q / TAPS, kw = TAPS == 3 ? q - ks * 3 : 1, ti = TAPS == 3 ? kw : 0;
-      if (q + 1 < NQ) {                                // next stage's x fragments
-        const int ks1 = (q + 1) / TAPS, kw1 = TAPS == 3 ? (q + 1) - ks1 * 3 : 1;
-        const int rr = ks1 >> 1, w0 = (ks1 & 1) * 16;
+    for (int q = 0; q < NQ; ++q) {                     // stage q = k step: 16 pixels of row rr = q >> 1
+      const int ks = q;
+      if (q + 1 < NQ) {                                // next stage's x fragments (centre tap: + 1 past the halo column)
+        const int rr = (q + 1) >> 1, w0 = ((q + 1) & 1) * 16;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int pl = 0; pl < 2; ++pl)
-            af[(q + 1) & 1][i][pl] = tr_read8h(xa + pl * X3_PLANE + i * X3_HALF + (rr * kPW + w0 + kw1) * 64);
+            af[(q + 1) & 1][i][pl] = tr_read8h(xa + pl * X3_PLANE + i * X3_HALF + (rr * kPW + w0 + 1) * 64);
       }
-      if ((TAPS == 1 || kw == 1) && ks + 1 < 4) {      // next k step's dy fragments
+      if (ks + 1 < 4) {                                // next k step's dy fragments
         const int rr = (ks + 1) >> 1, w0 = ((ks + 1) & 1) * 16;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -1082,17 +1040,11 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
           for (int pl = 0; pl < 2; ++pl)
             bfr[(ks + 1) & 1][j][pl] = tr_read8h(db + pl * D3_PLANE + j * D3_HALF + (rr * kW + w0) * 64);
       }
-      // staging, each register refilled at once with the same unit of pair p + 2.  TAPS = 3: x unit q in stages
-      // 0..8, dy unit q - 4 in stages 4..11.  TAPS = 1 (4 stages): units q, q + 4, (q + 8).
-      if (TAPS == 3) {
-        if (q < XV) { store_x(bn, q); gload_x1(pr2, q); }
-        if (q >= 4) { store_d(bn, q - 4); gload_d1(pr2, q - 4); }
-      } else {
+      // staging, each register refilled at once with the same unit of pair p + 2: units q, q + 4, (q + 8)
 #pragma unroll
-        for (int uu = q; uu < XV; uu += 4) { store_x(bn, uu); gload_x1(pr2, uu); }
+      for (int uu = q; uu < XV; uu += 4) { store_x(bn, uu); gload_x1(pr2, uu); }
 #pragma unroll
-        for (int uu = q; uu < DV; uu += 4) { store_d(bn, uu); gload_d1(pr2, uu); }
-      }
+      for (int uu = q; uu < DV; uu += 4) { store_d(bn, uu); gload_d1(pr2, uu); }
 #pragma unroll
       for (int term = 0; term < 3; ++term) {
         constexpr int PA[3] = {1, 0, 0};
@@ -1101,16 +1053,16 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            acc[ti][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[q & 1][i][PA[term]], bfr[ks & 1][j][PB[term]],
-                                                                   acc[ti][i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[q & 1][i][PA[term]], bfr[ks & 1][j][PB[term]],
+                                                               acc[i][j], 0, 0, 0);
       }
 #pragma unroll
       for (int g = 0; g < 12; ++g) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-        if (TAPS == 1 || (g & 3) == 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        if (TAPS == 1 || (g & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1121,21 +1073,18 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
   float sdummy, inv_x, inv_g;
   scale_of(xmax_of(b_acc), sdummy, inv_x);
   scale_of(row_max16(p.dymax, b_acc), sdummy, inv_g);
-  const int ntaps = TAPS == 3 ? 9 : 1;
-  float* slab = p.slab + (size_t)blockIdx.x * ntaps * C * N;
+  float* slab = p.slab + (size_t)blockIdx.x * C * N;
 #pragma unroll
-  for (int kw = 0; kw < TAPS; ++kw)
+  for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + wco * 64 + j * 32 + li;
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wco * 64 + j * 32 + li;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c = c0 + wci * 64 + i * 32 + mfma32_row(r, lane);
-          slab[((size_t)(TAPS == 3 ? kh * 3 + kw : 0) * C + c) * N + n] = (acc[kw][i][j][r] * inv_x) * inv_g;
-        }
+      for (int r = 0; r < 16; ++r) {
+        const int c = c0 + wci * 64 + i * 32 + mfma32_row(r, lane);
+        slab[(size_t)c * N + n] = (acc[i][j][r] * inv_x) * inv_g;
       }
+    }
   if (stamp) { p.stamps[23] = __builtin_amdgcn_s_memtime(); p.stamps[31] = __builtin_amdgcn_s_memrealtime(); }
 }
 
@@ -1326,11 +1275,6 @@ __global__ __launch_bounds__(W8_THREADS) void conv3x3_wgrad_f16x3_w16_kernel(Wgr
 #pragma unroll
     for (int i = 0; i < 4; ++i) gload_d1(i);
   }
-  // slab reductions handed over by earlier launches on this stream (their slabs are complete: stream order): a share of
-  // the outputs per block, behind the operand loads just issued -- a few microseconds of a prologue that waits for
-  // memory anyway, instead of a 576-block launch of its own behind every weight gradient (8.8 us alone, 15-55 us beside
-  // the main chain's kernels: profiles/r06_step_timeline.log)
-  for (int k = 0; k < p.npend; ++k) fold_slab_reduction(p.pend[k], blockIdx.x * W8_THREADS + tid, gridDim.x * W8_THREADS);
   __syncthreads();
   read_b(smem, 0, 0);
   read_a(smem, 0, 0, 0);
@@ -1732,8 +1676,7 @@ MULAN_API int mulan_conv3x3_wgrad_f16x3(const float* x, const unsigned* xmax, co
 }
 
 static int launch_wgrad_w16(const void* xs, const unsigned* xmax, const void* dys, const unsigned* dymax, float* workspace,
-                            int B, int H, int C, int N, int S8, const mulan_slab_reduction* pending, int n_pending,
-                            hipStream_t stream) {
+                            int B, int H, int C, int N, int S8, hipStream_t stream) {
   static bool configured16 = false;
   if (!configured16) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_f16x3_w16_kernel),
@@ -1743,44 +1686,9 @@ static int launch_wgrad_w16(const void* xs, const unsigned* xmax, const void* dy
   }
   WgradArgsP a8{static_cast<const unsigned char*>(xs), static_cast<const unsigned char*>(dys), xmax, dymax, workspace,
                 B, H, C, N, S8, g_mulan_debug_buffer};
-  a8.npend = n_pending;
-  for (int k = 0; k < n_pending; ++k) a8.pend[k] = pending[k];
   const dim3 grid8(3 * S8 * (C / WG3_T) * (N / WG3_T));
   hipLaunchKernelGGL(conv3x3_wgrad_f16x3_w16_kernel, grid8, dim3(W8_THREADS), WG3_SMEM + 64, stream, a8);
   return 0;
-}
-
-// ---- slab reductions folded into the NEXT weight-gradient launch (round 6).  In the backward pass of a train step the
-// 3x3 weight gradients follow one another on one stream; a launch made with _fold writes its slabs and does NOT sum
-// them: the caller hands the record {slab, out, S, E, accumulate} to a later _fold launch (up to two records per launch,
-// summed by its blocks' prologues in slab order: the bits of the separate reduction kernel) or to mulan_slab_reduce.
-MULAN_API int mulan_conv3x3_wgrad_f16x3_planes_splits(int B, int H, int W, int C, int N, int share_chip) {
-  if (W != kW || H % WG_ROWS != 0 || B <= 0 || C % WG3_T != 0 || N % WG3_T != 0) return 0;
-  return wgrad_splits_w8(B, H, C, N, share_chip);
-}
-
-MULAN_API int mulan_conv3x3_wgrad_f16x3_planes_fold(const void* xs, const unsigned* xmax, const void* dys,
-                                                    const unsigned* dymax, float* workspace, int B, int H, int W, int C,
-                                                    int N, int share_chip, const mulan_slab_reduction* pending,
-                                                    int n_pending, hipStream_t stream) {
-  if (W != kW || H % WG_ROWS != 0 || B <= 0 || C % WG3_T != 0 || N % WG3_T != 0 || !xs || !dys || !xmax || !dymax ||
-      !workspace || n_pending < 0 || n_pending > 2 || (n_pending > 0 && !pending) ||
-      (size_t)B * H * W * (C > N ? C : N) * 4 >= 0x80000000ull)
-    return (int)hipErrorInvalidValue;
-  for (int k = 0; k < n_pending; ++k)
-    if (!pending[k].slab || !pending[k].out || pending[k].S <= 0 || pending[k].E <= 0 || pending[k].E % 4 != 0 ||
-        (reinterpret_cast<uintptr_t>(pending[k].slab) | reinterpret_cast<uintptr_t>(pending[k].out)) % 16 != 0)
-      return (int)hipErrorInvalidValue;
-  const int rc = launch_wgrad_w16(xs, xmax, dys, dymax, workspace, B, H, C, N, wgrad_splits_w8(B, H, C, N, share_chip),
-                                  pending, n_pending, stream);
-  if (rc != 0) return rc;
-  MULAN_CHECK_LAUNCH();
-}
-
-MULAN_API int mulan_slab_reduce(const float* slab, float* out, int S, int E, int accumulate, hipStream_t stream) {
-  if (!slab || !out || S <= 0 || E <= 0) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(slab_reduce_h_kernel, dim3((E + 255) / 256), dim3(256), 0, stream, slab, out, S, E, accumulate);
-  MULAN_CHECK_LAUNCH();
 }
 
 MULAN_API size_t mulan_conv3x3_wgrad_f16x3_planes_workspace(int B, int H, int W, int C, int N, int share_chip) {
@@ -1797,7 +1705,7 @@ MULAN_API int mulan_conv3x3_wgrad_f16x3_planes(const void* xs, const unsigned* x
       (size_t)B * H * W * (C > N ? C : N) * 4 >= 0x80000000ull)
     return (int)hipErrorInvalidValue;
   const int S = wgrad_splits_w8(B, H, C, N, share_chip);
-  const int rc = launch_wgrad_w16(xs, xmax, dys, dymax, workspace, B, H, C, N, S, nullptr, 0, stream);
+  const int rc = launch_wgrad_w16(xs, xmax, dys, dymax, workspace, B, H, C, N, S, stream);
   if (rc != 0) return rc;
   const int E = 9 * C * N;
   hipLaunchKernelGGL(slab_reduce_h_kernel, dim3((E + 255) / 256), dim3(256), 0, stream, workspace, dw, S, E, accumulate);
@@ -1847,7 +1755,7 @@ MULAN_API int mulan_linear_wgrad_f16x3_planes(const void* xs, const unsigned* xm
     return (int)hipErrorInvalidValue;
   static bool configured = false;
   if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_f16x3_planes_kernel<1>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_f16x3_planes_kernel<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, WG3_SMEM + 64);
     if (e != hipSuccess) return (int)e;
     configured = true;
@@ -1855,7 +1763,7 @@ MULAN_API int mulan_linear_wgrad_f16x3_planes(const void* xs, const unsigned* xm
   const int S = linear_wgrad_splits(B, H, C, N, share_chip);
   WgradArgsP a{static_cast<const unsigned char*>(xs), static_cast<const unsigned char*>(dys), xmax, dymax, workspace,
                B, H, C, N, S, g_mulan_debug_buffer};
-  hipLaunchKernelGGL(conv3x3_wgrad_f16x3_planes_kernel<1>, dim3(S, 1, (C / WG3_T) * (N / WG3_T)), dim3(256),
+  hipLaunchKernelGGL(conv3x3_wgrad_f16x3_planes_kernel<false>, dim3(S, 1, (C / WG3_T) * (N / WG3_T)), dim3(256),
                      WG3_SMEM + 64, stream, a);
   const int E = C * N;
   hipLaunchKernelGGL(slab_reduce_h_kernel, dim3((E + 255) / 256), dim3(256), 0, stream, workspace, dw, S, E, accumulate);
@@ -1880,7 +1788,7 @@ MULAN_API int mulan_linear_wgrad_f16x3_x32(const float* x1, const float* x2, int
     return (int)hipErrorInvalidValue;
   static bool configured = false;
   if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_f16x3_planes_kernel<1, true>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_f16x3_planes_kernel<true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, WG3_SMEM + 64);
     if (e != hipSuccess) return (int)e;
     configured = true;
@@ -1888,7 +1796,7 @@ MULAN_API int mulan_linear_wgrad_f16x3_x32(const float* x1, const float* x2, int
   const int S = linear_wgrad_splits(B, H, C, N, share_chip);
   WgradArgsP a{nullptr, static_cast<const unsigned char*>(dys), xmax, dymax, workspace, B, H, C, N, S, g_mulan_debug_buffer,
                x1, x2, C1, C2 > 0 ? xmax2 : nullptr};
-  hipLaunchKernelGGL((conv3x3_wgrad_f16x3_planes_kernel<1, true>), dim3(S, 1, (C / WG3_T) * (N / WG3_T)), dim3(256),
+  hipLaunchKernelGGL((conv3x3_wgrad_f16x3_planes_kernel<true>), dim3(S, 1, (C / WG3_T) * (N / WG3_T)), dim3(256),
                      WG3_SMEM + 64, stream, a);
   const int E = C * N;
   hipLaunchKernelGGL(slab_reduce_h_kernel, dim3((E + 255) / 256), dim3(256), 0, stream, workspace, dw, S, E, accumulate);
@@ -1904,12 +1812,12 @@ MULAN_API int mulan_bmm_tn_f16x3_planes(const void* xs, const unsigned* xmax, co
   if (W != kW || H % WG_ROWS != 0 || B <= 0 || C % WG3_T != 0 || N % WG3_T != 0 || !xs || !dys || !xmax || !dymax || !out ||
       (size_t)B * H * W * (C > N ? C : N) * 4 >= 0x80000000ull)
     return (int)hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_f16x3_planes_kernel<1>),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_f16x3_planes_kernel<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, WG3_SMEM + 64);
   if (e != hipSuccess) return (int)e;
   WgradArgsP a{static_cast<const unsigned char*>(xs), static_cast<const unsigned char*>(dys), xmax, dymax, out,
                B, H, C, N, B, g_mulan_debug_buffer};
-  hipLaunchKernelGGL(conv3x3_wgrad_f16x3_planes_kernel<1>, dim3(B, 1, (C / WG3_T) * (N / WG3_T)), dim3(256),
+  hipLaunchKernelGGL(conv3x3_wgrad_f16x3_planes_kernel<false>, dim3(B, 1, (C / WG3_T) * (N / WG3_T)), dim3(256),
                      WG3_SMEM + 64, stream, a);
   MULAN_CHECK_LAUNCH();
 }

@@ -6,7 +6,6 @@ Shapes: images are [B, 1024, C] (NHWC with H = W = 32 flattened), matrices row-m
 By-products that one node leaves on a tensor for the next (maxima, statistics, channel sums, planes ...) go through
 _leave / _left / _carry below; DESIGN.md section 2 ("By-products travel with the tensor") lists the tags.
 """
-import ctypes
 import math
 import weakref
 
@@ -79,15 +78,11 @@ class weight_gradient_stream:
     def __enter__(self):
         _SIDE["active"] = SIDE_STREAM
         _SIDE["scope"] = True
-        _SLAB_PENDING.clear()            # (records of a backward pass that an exception cut short must not reach this one)
-        _SLAB_KEEP.clear()
         return self
 
     def __exit__(self, *exc):
-        flush_slab_reductions()          # (while the side stream is still the place where weight gradients run)
         _SIDE["active"] = False
         _SIDE["scope"] = False
-        _SLAB_KEEP.clear()
         side_join()
         return False
 
@@ -126,9 +121,6 @@ def _on_side(launch, keep):
         launch()
         done = torch.cuda.Event()
         done.record(side)
-    if _SLAB_KEEP:                   # (slab sets of earlier launches that this one summed: alive until it has run)
-        keep = (keep, tuple(_SLAB_KEEP))
-        _SLAB_KEEP.clear()
     pending.append((done, keep))
     while len(pending) > SIDE_DEPTH:
         main.wait_event(pending.popleft()[0])
@@ -145,6 +137,19 @@ def side_join():
 
 def _side_ok(sink):
     return _SIDE["active"] and sink is not None and sink.is_cuda
+
+
+def _wgrad_to_sink(sink, launch, keep, ok=True):
+    """a weight gradient written where its parameter's gradient lives: launch(out=a fresh view of `sink`, the parameter's
+    view of the flat gradient buffer; None without one: the launch then allocates) -- on the side stream when the scope
+    is active, the sink exists and `ok` (the caller's own condition) holds, in line otherwise.  `keep`: the tensors the
+    launch reads (_on_side).  Returns the very object it passed as `out` (or what launch allocated): autograd's
+    AccumulateGrad adopts a gradient without a copy only while nothing else refers to it."""
+    if ok and _side_ok(sink):
+        dw = _fresh(sink)
+        _on_side(lambda: launch(out=dw), keep)
+        return dw
+    return launch(out=_fresh(sink) if sink is not None else None)
 
 
 def absmax_rows(x):
@@ -568,66 +573,9 @@ def conv3x3_wgrad_raw(x, dy, out=None, xmax=None, dymax=None):
     return dw
 
 
-# ---- slab reductions folded into the next weight-gradient launch (round 6; mulan_conv3x3_wgrad_f16x3_planes_fold)
-# Inside the backward pass of a train step (a weight_gradient_stream() scope) a 3x3 weight gradient writes its slabs and
-# leaves the record (workspace, dw, S, E) here; the next one sums them in the prologue of its blocks, and whatever is
-# still pending when a gradient bucket is complete (parallel.GradReducer) or the pass ends is summed by
-# mulan_slab_reduce.  Same summation order, same bits as the reduction launch behind every weight gradient that this
-# replaces (146 launches of a train step).  Built for VERDICT r05 item 8 (<= 1000 launches per step) and MEASURED: the
-# replayed step at B = 128 takes 75.15 / 75.17 ms with the fold against 74.87 / 75.07 ms without (alternating runs, one
-# box, profiles/r06_fold_slab_reduce_ab.log) -- the 8.8 us reduction launches were never the cost, their bytes are, and
-# the prologue of a 120-block launch sums them no faster than 576 small blocks do.  OPT-IN (MULAN_FOLD_SLAB_REDUCE=1):
-# the default keeps the reduction launch behind every weight gradient; bit-identical either way
-# (tests/test_gpu_f16x3.py::test_f16x3_slab_reductions_folded_into_the_next_weight_gradient, tools/fold_check.py).
-FOLD_SLAB_REDUCE = _os.environ.get("MULAN_FOLD_SLAB_REDUCE", "0") == "1"
-_SLAB_PENDING = []        # [(workspace, dw, S, E)]
-_SLAB_KEEP = []           # tensors the launch just issued reads beyond its own arguments (_on_side keeps them alive)
-
-
-def _pending_array(recs):
-    arr = (lib.SlabReduction * max(1, len(recs)))()
-    for i, (ws, dw, S, E) in enumerate(recs):
-        arr[i].slab, arr[i].out, arr[i].S, arr[i].E, arr[i].accumulate = ws.data_ptr(), dw.data_ptr(), S, E, 0
-    return arr
-
-
-def flush_slab_reductions():
-    """sum every pending slab set now (before anything reads those weight gradients: the all-reduce of their bucket, the
-    optimizer).  Issued where the weight gradients run: on the side stream while it is active."""
-    if not _SLAB_PENDING:
-        return
-    recs = list(_SLAB_PENDING)
-    _SLAB_PENDING.clear()
-
-    def launch():
-        for ws, dw, S, E in recs:
-            call("mulan_slab_reduce", ptr(ws), ptr(dw), S, E, 0, stream())
-    if _SIDE["active"] and recs[0][0].is_cuda:
-        _on_side(launch, tuple(t for r in recs for t in r[:2]))
-    else:
-        launch()
-
-
 def conv3x3_wgrad_planes_raw(xs, xmax, dys, dymax, B, C, N, out=None):
     """dw from the split planes of x (written by the forward conv) and of dy (written by the input-gradient conv)"""
     share = _share_chip()
-    if FOLD_SLAB_REDUCE and _SIDE["scope"] and out is not None:
-        L = lib.load()
-        S = L.mulan_conv3x3_wgrad_f16x3_planes_splits(B, H, W, C, N, share)
-        E = 9 * C * N
-        ws = torch.empty(S * E, device=xs.device, dtype=torch.float32)
-        take = _SLAB_PENDING[:2]
-        del _SLAB_PENDING[:2]
-        arr = _pending_array(take)
-        _timed("conv3x3_wgrad_f16x3_planes_kernel+slab_reduce", 2.0 * B * HW * 9 * C * N,
-               lambda: call("mulan_conv3x3_wgrad_f16x3_planes_fold", ptr(xs), ptr(xmax), ptr(dys), ptr(dymax), ptr(ws), B, H,
-                            W, C, N, share, ctypes.addressof(arr) if take else None, len(take), stream()))
-        _SLAB_KEEP.extend(t for r in take for t in r[:2])
-        # (the record holds ANOTHER tensor object over dw's storage: a second reference to `out` itself would keep
-        # autograd's AccumulateGrad from adopting it -- it would clone the not yet written gradient instead, and
-        # TrainState.collect_grads would copy that clone over the real one)
-        _SLAB_PENDING.append((ws, _fresh(out), S, E))
-        return out
     nbytes = lib.load().mulan_conv3x3_wgrad_f16x3_planes_workspace(B, H, W, C, N, share)
     ws = torch.empty(nbytes // 4, device=xs.device, dtype=torch.float32)
     dw = out if out is not None else torch.empty((3, 3, C, N), device=xs.device, dtype=torch.float32)
@@ -735,13 +683,9 @@ def _conv3x3_backward(ctx, dy):
     want_max = bool(getattr(ctx, "want_dx_max", False))
 
     def wgrad_from_planes(dys, dymax):
-        if _side_ok(gvw):
-            dw_, xmax = _fresh(gvw), ctx.xmax
-            _on_side(lambda: conv3x3_wgrad_planes_raw(x, xmax, dys, dymax, B, w.shape[2], N, out=dw_),
-                     (x, xmax, dys, dymax))
-            return dw_
-        return conv3x3_wgrad_planes_raw(x, ctx.xmax, dys, dymax, B, w.shape[2], N,
-                                        out=_fresh(gvw) if gvw is not None else None)
+        xmax = ctx.xmax
+        return _wgrad_to_sink(gvw, lambda out: conv3x3_wgrad_planes_raw(x, xmax, dys, dymax, B, w.shape[2], N, out=out),
+                              (x, xmax, dys, dymax))
 
     gp = _left(dy, "_grad_planes")
     if gp is not None:
@@ -771,12 +715,9 @@ def _conv3x3_backward(ctx, dy):
                   if ctx.needs_input_grad[0] else None)
             dw = None
             if ctx.needs_input_grad[1]:   # written straight into the flat gradient buffer when the weight is a leaf
-                if _side_ok(gvw) and (dymax is None or ctx.xmax is not None):
-                    dw, xmax = _fresh(gvw), ctx.xmax
-                    _on_side(lambda: conv3x3_wgrad_raw(x, dy, out=dw, xmax=xmax, dymax=dymax), (x, dy, xmax, dymax))
-                else:
-                    dw = conv3x3_wgrad_raw(x, dy, out=_fresh(gvw) if gvw is not None else None, xmax=ctx.xmax,
-                                           dymax=dymax)
+                xmax = ctx.xmax
+                dw = _wgrad_to_sink(gvw, lambda out: conv3x3_wgrad_raw(x, dy, out=out, xmax=xmax, dymax=dymax),
+                                    (x, dy, xmax, dymax), ok=dymax is None or xmax is not None)
     dbias = dcb = None
     per_sample = None
     parts = _left(dy, "_colsum_parts")                 # left by TeeFn.backward's add: 16 partial column sums per image
@@ -953,11 +894,8 @@ class LinearFn(torch.autograd.Function):
                 dx = gemm_raw(dy2, w, M, K, N, transB=True).view(xshape)
         gvw, gvb = ctx.gv
         if ctx.needs_input_grad[1]:
-            if _side_ok(gvw) and M >= 4096:          # (the small per-sample layers stay in line: nothing to overlap)
-                dw = _fresh(gvw)
-                _on_side(lambda: gemm_raw(x2, dy2, K, N, M, transA=True, out=dw), (x2, dy2))
-            else:
-                dw = gemm_raw(x2, dy2, K, N, M, transA=True, out=_fresh(gvw) if gvw is not None else None)
+            dw = _wgrad_to_sink(gvw, lambda out: gemm_raw(x2, dy2, K, N, M, transA=True, out=out), (x2, dy2),
+                                ok=M >= 4096)          # (the small per-sample layers stay in line: nothing to overlap)
         if has_bias and ctx.needs_input_grad[2]:
             db = _dense_bias_grad(dy, M, N, gvb)
         dres = dy if (has_res and ctx.needs_input_grad[3]) else None
@@ -1096,32 +1034,26 @@ class Linear2Fn(torch.autograd.Function):
         dw = None
         gvw, gvb = ctx.gv
         if ctx.needs_input_grad[2]:
-            dw = _fresh(gvw) if gvw is not None else torch.empty_like(w)
             pl = _left(dy, "_planes")       # (planes of dy, its maxima) left by the convolution that consumed the same dy
             x32 = getattr(ctx, "x32", None)
             if x32 is not None and pl is not None and pl[0].numel() == M * N * 4:
                 B_ = M // HW
                 x1v, x2v = a1.view(B_, HW, K1), a2.view(B_, HW, K2)
-                if _side_ok(gvw):
-                    _on_side(lambda: linear_wgrad_x32_raw(x1v, x2v, x32[0], x32[1], pl[0], pl[1], B_, N, out=dw),
-                             (x1v, x2v, x32[0], x32[1], pl[0], pl[1]))
-                else:
-                    linear_wgrad_x32_raw(x1v, x2v, x32[0], x32[1], pl[0], pl[1], B_, N, out=dw)
+                dw = _wgrad_to_sink(
+                    gvw, lambda out: linear_wgrad_x32_raw(x1v, x2v, x32[0], x32[1], pl[0], pl[1], B_, N, out=out),
+                    (x1v, x2v, x32[0], x32[1], pl[0], pl[1]))
             elif ctx.xs is not None and pl is not None and pl[0].numel() == M * N * 4:
-                if _side_ok(gvw):
-                    xs, xsmax = ctx.xs, ctx.xsmax
-                    _on_side(lambda: linear_wgrad_planes_raw(xs, xsmax, pl[0], pl[1], M // HW, K1 + K2, N, out=dw),
-                             (xs, xsmax, pl[0], pl[1]))
-                else:
-                    linear_wgrad_planes_raw(ctx.xs, ctx.xsmax, pl[0], pl[1], M // HW, K1 + K2, N, out=dw)
-            elif _side_ok(gvw):
-                def both():
-                    gemm_raw(a1, dy2, K1, N, M, transA=True, out=dw[:K1])
-                    gemm_raw(a2, dy2, K2, N, M, transA=True, out=dw[K1:])
-                _on_side(both, (a1, a2, dy2))
+                xs, xsmax = ctx.xs, ctx.xsmax
+                dw = _wgrad_to_sink(
+                    gvw, lambda out: linear_wgrad_planes_raw(xs, xsmax, pl[0], pl[1], M // HW, K1 + K2, N, out=out),
+                    (xs, xsmax, pl[0], pl[1]))
             else:
-                gemm_raw(a1, dy2, K1, N, M, transA=True, out=dw[:K1])
-                gemm_raw(a2, dy2, K2, N, M, transA=True, out=dw[K1:])
+                def both(out):
+                    out = torch.empty_like(w) if out is None else out
+                    gemm_raw(a1, dy2, K1, N, M, transA=True, out=out[:K1])
+                    gemm_raw(a2, dy2, K2, N, M, transA=True, out=out[K1:])
+                    return out
+                dw = _wgrad_to_sink(gvw, both, (a1, a2, dy2))
         db = None
         if ctx.needs_input_grad[3]:
             db = _dense_bias_grad(dy, M, N, gvb)

@@ -170,13 +170,11 @@ def test_f16x3_zero_operands(ops):
 
 
 @pytest.mark.parametrize("side", [False, True])
-def test_f16x3_slab_reductions_folded_into_the_next_weight_gradient(ops, side, monkeypatch):
-    """mulan_conv3x3_wgrad_f16x3_planes_fold (round 6): inside a weight_gradient_stream() scope -- the backward pass of a
-    train step -- a 3x3 weight gradient writes its slabs and leaves them to the NEXT one, whose blocks sum them in their
-    prologue (up to two sets per launch); what is pending at the end of the scope goes to mulan_slab_reduce.  A chain of
-    four weight gradients of three shapes (and one extra flush in the middle, as a completed gradient bucket forces it)
-    gives the very bits of the four stand-alone launches with their own reduction kernels -- same slabs, same summation
-    order -- with the weight-gradient stream on and off; on integer data both are exact."""
+def test_f16x3_weight_gradients_inside_the_weight_gradient_stream_scope(ops, side, monkeypatch):
+    """inside a weight_gradient_stream() scope -- the backward pass of a train step -- a chain of four plane-fed 3x3
+    weight gradients of three shapes, issued through _on_side (weight-gradient stream on) or directly (off), gives the
+    very bits of the four stand-alone launches -- same slabs, same summation order, one
+    mulan_conv3x3_wgrad_f16x3_planes call each -- and on integer data both are exact."""
     import mulan_amd.ops as O
     rng = np.random.default_rng(5)
     B = 3
@@ -193,7 +191,6 @@ def test_f16x3_slab_reductions_folded_into_the_next_weight_gradient(ops, side, m
         tr.conv3x3(xt, {"kernel": wt}).backward(torch.tensor(dy))
         cases.append((xs, xmax, dys, dymax, C, N, wt.grad.numpy()))
     monkeypatch.setattr(O, "SIDE_STREAM", side)
-    monkeypatch.setattr(O, "FOLD_SLAB_REDUCE", True)      # (opt-in: measured +-0 on the train step, ops.FOLD_SLAB_REDUCE)
     monkeypatch.setattr(O, "SIDE_WGRAD_SHARE", False)     # the same split count inside and outside the scope
     alone = [ops.conv3x3_wgrad_planes_raw(xs, xm, dys, dm, B, C, N, out=torch.empty(3, 3, C, N, device="cuda"))
              for xs, xm, dys, dm, C, N, _ in cases]
@@ -202,20 +199,14 @@ def test_f16x3_slab_reductions_folded_into_the_next_weight_gradient(ops, side, m
     orig = O.call
     monkeypatch.setattr(O, "call", lambda name, *a: (names.append(name), orig(name, *a))[1])
     with O.weight_gradient_stream():
-        for i, ((xs, xm, dys, dm, C, N, _), o) in enumerate(zip(cases, outs)):
+        for (xs, xm, dys, dm, C, N, _), o in zip(cases, outs):
             launch = lambda xs=xs, xm=xm, dys=dys, dm=dm, C=C, N=N, o=o: ops.conv3x3_wgrad_planes_raw(xs, xm, dys, dm, B, C, N, out=o)
             if side:
                 O._on_side(launch, (xs, xm, dys, dm))
             else:
                 launch()
-            if i == 1:
-                O.flush_slab_reductions()           # (a completed gradient bucket: parallel.GradReducer._launch)
-                assert not O._SLAB_PENDING
-        assert len(O._SLAB_PENDING) == 1            # the third set went into the fourth launch; the fourth is pending
     torch.cuda.synchronize()
-    assert not O._SLAB_PENDING and not O._SLAB_KEEP
-    assert names.count("mulan_conv3x3_wgrad_f16x3_planes_fold") == 4 and names.count("mulan_slab_reduce") == 2
-    assert "mulan_conv3x3_wgrad_f16x3_planes" not in names
+    assert names == ["mulan_conv3x3_wgrad_f16x3_planes"] * 4
     for (_, _, _, _, C, N, ref), a, o in zip(cases, alone, outs):
         assert torch.equal(a, o)
         assert np.array_equal(o.cpu().double().numpy(), ref)
