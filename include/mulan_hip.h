@@ -553,6 +553,21 @@ int mulan_poly_gamma_fwd(const float* a, const float* b, const float* c, const f
 int mulan_poly_gamma_bwd(const float* a, const float* b, const float* c, const float* t, const float* dgt,
                          const float* dgprime, float* da, float* db, float* dc, int B, int d, float gamma_min,
                          float gamma_max, mulan_stream_t stream);
+/* The mean schedule of a batch, for time grids of the few-step samplers (not in the reference).  With the end points
+ * fixed, gamma_i(t) = gamma_min + (gamma_max - gamma_min) P_i(t) / S_i with P_i a quintic without constant term, so the
+ * mean over sub-pixels and samples is gamma_bar(t) = gamma_min + (gamma_max - gamma_min) sum_{k=1..5} m_k t^k.
+ * mulan_schedule_moments writes m_out[B][5]: per sample the means over its d sub-pixels of
+ * (c^2, b c, (b^2 + 2 a c) / 3, a b / 2, a^2 / 5) / S.  One block per sample, fp32, one fixed summation order (no
+ * atomics: the same bits on every run); S is evaluated as a sum of squares, without the cancellation of the monomial
+ * form.  hipErrorInvalidValue for a NULL pointer, B < 1, d != 3072. */
+int mulan_schedule_moments(const float* a, const float* b, const float* c, int B, int d, float* m_out,
+                           mulan_stream_t stream);
+/* t_out[i] = the t in [0, 1] with gamma_bar(t) = targets[i], gamma_bar from the mean of the B rows of m (summed in
+ * double in the order b = 0 .. B - 1): bisection on the quintic in double, 48 halvings of [0, 1], rounded to fp32 once.
+ * A target >= gamma_max (or NaN) returns exactly 1, a target <= gamma_min exactly 0.  One thread per target.
+ * hipErrorInvalidValue for a NULL pointer, B < 1, M < 1, gamma_min >= gamma_max. */
+int mulan_schedule_invert(const float* m, int B, const double* targets, int M, double gamma_min, double gamma_max,
+                          float* t_out, mulan_stream_t stream);
 /* discrete-time (T > 0) loss weight w = T * expm1(gamma_t - gamma_s) (model_mulan_epsilon.py:348-355) */
 int mulan_expm1_weight_fwd(const float* gt, const float* gs, float* w, size_t n, float T, mulan_stream_t stream);
 int mulan_expm1_weight_bwd(const float* gt, const float* gs, const float* dw, float* dgt, float* dgs, size_t n,

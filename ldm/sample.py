@@ -1,6 +1,7 @@
 """python -m ldm.sample --config=... --checkpoint_directory=... [--checkpoint N] --n_samples=N --out=FILE.npz
                       [--sampler dpm2m|sde2m|ddim|ancestral] [--eta 0.0] [--steps 25] [--batch_size B]
                       [--embedding deterministic|random] [--seed 0]
+                      [--grid uniform|logsnr|karras|quadratic [--grid_rho 7]]
                       [--inpaint_images=FILE.npz [--mask box:y0,x0,y1,x1|half:left|right|top|bottom] [--resample 1]]
                       [--restore_images=FILE.npz [--degradation sr:4|gray|sr:4+gray] [--resample 1]]
 
@@ -10,6 +11,10 @@ is drawn from PRNGKey(seed).fold_in(b) alone (the step noise of sde2m and of ddi
 three sub-keys, folded with the step index: Experiment_Colab.sample_batches); under torchrun the batches are dealt
 round-robin to the ranks and rank 0 writes the file, so for a fixed --batch_size the file does not depend on the number
 of ranks.  The flags are checked before any device is touched.
+
+--grid names the time grid of a few-step sampler (mulan_amd.sampling.make_grid): uniform in t (the default), quadratic
+in t, or -- on the mean schedule of each batch's own embeddings, so a batch still depends on its key alone -- uniform in
+the log signal-to-noise ratio (logsnr) or the EDM grid with --grid_rho (karras).
 
 --inpaint_images=FILE.npz (array `images`, uint8 [N, 32, 32, 3], and optionally `mask`, [N, 32, 32] or [32, 32],
 non-zero = keep) inpaints instead: image b B + j goes to slot j of global batch b, its kept pixels come back as they went
@@ -39,7 +44,7 @@ import numpy as np
 
 from mulan_amd.config import Flags
 from mulan_amd import checkpoint as ckpt_lib
-from mulan_amd.sampling import SAMPLERS
+from mulan_amd.sampling import SAMPLERS, check_grid
 
 EMBEDDINGS = ('deterministic', 'random')
 
@@ -56,6 +61,8 @@ def make_flags():
     flags.DEFINE_integer('batch_size', None, 'Images per batch (default: config.training.batch_size_eval).')
     flags.DEFINE_string('embedding', 'deterministic', 'deterministic / random latent embedding of the MuLAN models.')
     flags.DEFINE_integer('seed', 0, 'Global batch b is drawn from PRNGKey(seed).fold_in(b).')
+    flags.DEFINE_string('grid', 'uniform', 'Time grid of ddim / dpm2m / sde2m: uniform / logsnr / karras / quadratic.')
+    flags.DEFINE_float('grid_rho', 7.0, '--grid=karras: the exponent rho, finite and > 0.')
     flags.DEFINE_string('inpaint_images', None, 'Inpaint the images of this .npz (images, optionally mask).')
     flags.DEFINE_string('mask', None, 'box:y0,x0,y1,x1 (unknown box) / half:left|right|top|bottom (kept half).')
     flags.DEFINE_integer('resample', 1, 'Inpainting and restoration: passes per step (1: no resampling).')
@@ -165,6 +172,10 @@ def parse_all(argv):
         raise SystemExit(f"--eta must lie in [0, 1], got {flags.eta!r}")
     if flags.eta != 0.0 and flags.sampler != 'ddim':
         raise SystemExit(f"--eta applies to --sampler=ddim; {flags.sampler!r} takes none")
+    try:
+        check_grid(flags.sampler, flags.grid, None, flags.grid_rho)
+    except ValueError as e:
+        raise SystemExit(f"--grid: {e}") from None
     inpaint = inpaint_inputs(flags)
     restore = restore_inputs(flags)
     given = inpaint[0] if inpaint else restore.array if restore else None     # the input images, or their measurements
@@ -242,7 +253,7 @@ def main(argv):
         kw = dict(measurement=[y_all[b * batch_size:(b + 1) * batch_size].contiguous() for b in mine],
                   degradation=restore.spec, resample=flags.resample)
     images = experiment.sample_batches([root.fold_in(b) for b in mine], batch_size, flags.embedding, flags.sampler,
-                                       flags.steps, flags.eta, **kw)
+                                       flags.steps, flags.eta, grid=flags.grid, grid_rho=flags.grid_rho, **kw)
     local = torch.zeros((per_rank, batch_size, 32, 32, 3), dtype=torch.uint8, device=experiment.device)
     for j, x in enumerate(images):
         local[j].copy_(x)
@@ -252,7 +263,7 @@ def main(argv):
         out = ordered.reshape(-1, 32, 32, 3)[:n_samples]
         settings = dict(sampler=flags.sampler, eta=float(flags.eta), steps=flags.steps, n_samples=n_samples,
                         batch_size=batch_size, embedding=flags.embedding, seed=flags.seed, checkpoint=str(ckpt_num),
-                        vdm_type=flags.config.get('vdm_type', 'vdm'))
+                        vdm_type=flags.config.get('vdm_type', 'vdm'), grid=flags.grid, grid_rho=float(flags.grid_rho))
         arrays = dict(images=out)
         if inpaint is not None:
             settings.update(inpaint=True, resample=flags.resample, mask=flags.mask)

@@ -37,13 +37,13 @@ class Experiment_Colab(Experiment_VDM):
         self.rngs = {'sample': sample_rng}
 
     # ---- samplers of the notebook front end (ldm/notebook_utils.py:54-135) --------------------------------------
-    def _embedding_samples(self, embedding, rng, T, sampler='ancestral', eta=0.0):
+    def _embedding_samples(self, embedding, rng, T, sampler='ancestral', eta=0.0, grid='uniform', grid_rho=7.0):
         """T steps of `sampler` under a fixed [B, 50] embedding (ancestral: model.conditional_sample), then generate_x
         (Experiment_VDM.draw_samples; z_1 ~ N(0, I) as the notebook draws it)"""
         rng = rng.fold_in(self.rank)
         rng, sample_rng = rng.split()
         samples, _ = self.draw_samples(self.params, embedding.shape[0], embedding, sample_rng, rng, rng.fold_in(T),
-                                       sampling.check_sampler(sampler), T, eta=eta)
+                                       sampling.check_sampler(sampler), T, eta=eta, grid=grid, grid_rho=grid_rho)
         return parallel.all_gather_tensor(samples)
 
     @staticmethod
@@ -53,25 +53,28 @@ class Experiment_Colab(Experiment_VDM):
             return T
         return 1000 if sampling.check_sampler(sampler) == 'ancestral' else 25
 
-    def sample_conditionally(self, embedding, T=None, sampler='ancestral', eta=0.0):
-        """Experiment_Colab.sample_conditionally: an image grid sampled under one 50-dim k-hot embedding (sampler, eta:
-        see Experiment_VDM.sample_fn; T is the step count, by default 1000 ancestral / 25 few-step)"""
+    def sample_conditionally(self, embedding, T=None, sampler='ancestral', eta=0.0, grid='uniform', grid_rho=7.0):
+        """Experiment_Colab.sample_conditionally: an image grid sampled under one 50-dim k-hot embedding (sampler, eta,
+        grid, grid_rho: see Experiment_VDM.sample_fn; T is the step count, by default 1000 ancestral / 25 few-step)"""
         sampling.check_eta(sampler, eta)
+        sampling.check_grid(sampler, grid, None, grid_rho)
         B = self.eval_iter.local
         emb = torch.as_tensor(embedding, dtype=torch.float32, device=self.device).reshape(1, -1)
         assert emb.shape[1] == 50
         samples = self._embedding_samples(emb.expand(B, 50).contiguous(), self.rng, self._steps(T, sampler), sampler,
-                                          eta)
+                                          eta, grid, grid_rho)
         return ckpt_lib.generate_image_grids(samples).astype(np.uint8)
 
-    def sample_randomly(self, T=None, sampler='ancestral', eta=0.0):
-        """Experiment_Colab.sample_randomly: every image under the hard top-15 embedding of its own random logits"""
+    def sample_randomly(self, T=None, sampler='ancestral', eta=0.0, grid='uniform', grid_rho=7.0):
+        """Experiment_Colab.sample_randomly: every image under the hard top-15 embedding of its own random logits
+        (grid, grid_rho: the time grid of a few-step sampler, see Experiment_VDM.sample_fn)"""
         from . import ops
         sampling.check_eta(sampler, eta)
+        sampling.check_grid(sampler, grid, None, grid_rho)
         B = self.eval_iter.local
         _, embeddings_rng = self.rng.fold_in(self.rank).split()
         emb, _ = ops.topk_hard(embeddings_rng.normal((B, 50), self.device), 15)
-        samples = self._embedding_samples(emb, self.rng, self._steps(T, sampler), sampler, eta)
+        samples = self._embedding_samples(emb, self.rng, self._steps(T, sampler), sampler, eta, grid, grid_rho)
         return ckpt_lib.generate_image_grids(samples).astype(np.uint8)
 
     KNOWN_NOISE_FOLD = 0x6B6E6F776E5F7869        # fold_in tag of a batch's known-region key: no step count reaches it
@@ -119,7 +122,7 @@ class Experiment_Colab(Experiment_VDM):
         return None
 
     def sample_batches(self, keys, batch_size, embedding='deterministic', sampler='dpm2m', steps=25, eta=0.0, known=None,
-                       mask=None, resample=1, measurement=None, degradation=None):
+                       mask=None, resample=1, measurement=None, degradation=None, grid='uniform', grid_rho=7.0):
         """uint8 [batch_size, 32, 32, 3] per key, each batch drawn from its key alone (the python -m ldm.sample CLI):
         key.split(3) -> (prior z_1 ~ sigma_prior N(0, I), random embedding logits, per-step noise); generate_x with
         key.fold_in(steps).  The per-step noise of the ancestral sampler, of sde2m and of ddim with eta > 0 comes from
@@ -136,8 +139,11 @@ class Experiment_Colab(Experiment_VDM):
         measurement (one per key: fp32 in the scale of ops.encode_u8, shaped ops.restore_y_shape) and degradation
         ('sr:f', 'gray' or 'sr:f+gray', one for all): restoration instead (draw_samples), `resample` passes per step.
         The jumps of resample > 1 draw from the same fourth sub-key; resample = 1 draws nothing from it.  The embeddings
-        of inpainting apply, 'encoder' on the replicated measurement A+ y rounded to 8-bit levels."""
+        of inpainting apply, 'encoder' on the replicated measurement A+ y rounded to 8-bit levels.
+        grid, grid_rho: the kind of time grid of a few-step sampler (sampling.GRIDS).  'logsnr' and 'karras' are spaced
+        on the mean schedule of the batch's own embeddings, so a batch still depends on its key alone."""
         sampling.check_eta(sampler, eta)
+        sampling.check_grid(sampler, grid, None, grid_rho)
         keys = list(keys)
         inpaint, restore, resample = sampling.check_guidance(sampler, known, mask, measurement, degradation, resample)
         if restore is not None:
@@ -163,11 +169,12 @@ class Experiment_Colab(Experiment_VDM):
                                         kw.get("measurement"), restore)
             x, stepper = self.draw_samples(self.params, batch_size, emb, k_z, k_s, key.fold_in(steps), sampler, steps,
                                            prior_scale=float(self.config.model.sigma_prior), stepper=stepper, eta=eta,
-                                           **kw)
+                                           grid=grid, grid_rho=grid_rho, **kw)
             out.append(x)
         return out
 
-    def inpaint(self, images, mask, embedding='deterministic', sampler='sde2m', steps=25, eta=0.0, resample=1, rng=None):
+    def inpaint(self, images, mask, embedding='deterministic', sampler='sde2m', steps=25, eta=0.0, resample=1, rng=None,
+                grid='uniform', grid_rho=7.0):
         """uint8 [B, 32, 32, 3]: `images` (uint8 [B, 32, 32, 3]) with the sub-pixels outside `mask` (bool or uint8
         [32, 32], [B, 32, 32] or [B, 32, 32, 3], True = keep) drawn by a few-step sampler (ddim with eta, dpm2m, sde2m)
         that overwrites the kept ones after every step with their own alpha_t x + sigma_t eps (sampling.run;
@@ -175,16 +182,16 @@ class Experiment_Colab(Experiment_VDM):
         back as they went in, with no paste-over.  embedding: 'deterministic', 'random', 'encoder' (MuLAN models: the hard
         top-k of apply_encoder on the images with the unknown pixels set to 128) or a k-hot tensor [50] or [B, 50].
         rng (default: the experiment's key) is folded with the rank and then split as sample_batches splits a batch's
-        key, so the same rng gives the same bytes."""
+        key, so the same rng gives the same bytes.  grid, grid_rho: the time grid, as sample_batches takes it."""
         images = torch.as_tensor(images)
         if images.dtype != torch.uint8 or images.dim() != 4 or tuple(images.shape[1:]) != (32, 32, 3):
             raise ValueError(f"images are uint8 [B, 32, 32, 3], got {images.dtype} {list(images.shape)}")
         key = (self.rng if rng is None else rng).fold_in(self.rank)
         return self.sample_batches([key], images.shape[0], embedding, sampler, steps, eta, known=[images], mask=[mask],
-                                   resample=resample)[0]
+                                   resample=resample, grid=grid, grid_rho=grid_rho)[0]
 
     def restore(self, images=None, measurement=None, degradation='sr:4', embedding='deterministic', sampler='sde2m',
-                steps=25, eta=0.0, resample=1, rng=None):
+                steps=25, eta=0.0, resample=1, rng=None, grid='uniform', grid_rho=7.0):
         """(restored uint8 [B, 32, 32, 3], residual fp32 [B]): images consistent with a degraded observation, drawn by a
         few-step sampler whose every prediction is projected onto the measurement (sampling.run).
         degradation: 'sr:f' (the f x f average-pooled image, f in 2, 4, 8, 16), 'gray' (the channel mean) or 'sr:f+gray'.
@@ -193,7 +200,7 @@ class Experiment_Colab(Experiment_VDM):
         are encoded like an image).  residual: the largest |A encode(restored) - y| of each image in grey levels
         (x 127.5): what per-pixel schedules inside a group and the 8-bit decoding leave of A x = y; reported, not
         asserted.  resample = U > 1: U passes per step.  embedding as inpaint takes it, 'encoder' on the replicated
-        measurement.  rng as inpaint."""
+        measurement.  rng as inpaint.  grid, grid_rho: the time grid, as sample_batches takes it."""
         from . import ops
         f, gray = sampling.parse_degradation(degradation)
         if (images is None) == (measurement is None):
@@ -215,7 +222,7 @@ class Experiment_Colab(Experiment_VDM):
             y = ops.encode_u8(y) if y.dtype == torch.uint8 else y.contiguous()
         key = (self.rng if rng is None else rng).fold_in(self.rank)
         out = self.sample_batches([key], B, embedding, sampler, steps, eta, resample=resample, measurement=[y],
-                                  degradation=degradation)[0]
+                                  degradation=degradation, grid=grid, grid_rho=grid_rho)[0]
         back = ops.restore_measure(ops.encode_u8(out), f, gray)
         return out, (back - y).abs().reshape(B, -1).amax(dim=1) * 127.5
 

@@ -486,8 +486,11 @@ class Experiment(abc.ABC):
         micro-batch, samples of all ranks concatenated.  T: config.training.sample_timesteps, default 1000 like the
         reference's hard-coded value; 0 disables sampling at evaluation points.  config.training.sampler (optional, not in
         the reference): 'ancestral' (the default), 'ddim', 'dpm2m' or 'sde2m', which then run sample_timesteps steps
-        (default 25)."""
+        (default 25); config.training.sampler_grid (optional): the kind of time grid of those three (sampling.GRIDS,
+        default 'uniform'), config.training.sampler_grid_rho the rho of 'karras' (default 7)."""
         sampler = sampling.check_sampler(self.config.training.get('sampler', 'ancestral'))
+        grid, rho = sampling.check_grid(sampler, self.config.training.get('sampler_grid', 'uniform'), None,
+                                        self.config.training.get('sampler_grid_rho', 7.0))
         if T is None:
             T = int(self.config.training.get('sample_timesteps', 1000 if sampler == 'ancestral' else 25))
         if T <= 0:
@@ -496,7 +499,8 @@ class Experiment(abc.ABC):
             self._sample_dummy = torch.empty((self.eval_iter.local, 32, 32, 3), dtype=torch.uint8, device=self.device)
         if sampler == 'ancestral':
             return self.sample_fn(dummy_inputs=self._sample_dummy, rng=self._sample_rng, params=params, T=T)
-        return self.sample_fn(dummy_inputs=self._sample_dummy, rng=self._sample_rng, params=params, T=T, sampler=sampler)
+        return self.sample_fn(dummy_inputs=self._sample_dummy, rng=self._sample_rng, params=params, T=T, sampler=sampler,
+                              grid=grid, grid_rho=rho)
 
     def _write_samples(self, writer, step, params):
         samples = self.p_sample(params)
@@ -566,7 +570,8 @@ class Experiment_VDM(Experiment):
         metrics = {'scalars': scalar_dict, 'images': {'inputs': inputs['images']}}
         return bpd, metrics
 
-    def sample_fn(self, *, dummy_inputs, rng, params, T=1000, gather=True, sampler='ancestral', t_grid=None, eta=0.0):
+    def sample_fn(self, *, dummy_inputs, rng, params, T=1000, gather=True, sampler='ancestral', t_grid=None, eta=0.0,
+                  grid='uniform', grid_rho=7.0):
         """Experiment_VDM.sample_fn (ldm/experiment_vdm.py:80-110): z_T ~ sigma_prior N(0, I), T ancestral steps
         (`model.sample`), `model.generate_x`; returns uint8 samples [B (* world), 32, 32, 3].  The noise stream is this
         build's Philox, folded with the rank like the reference folds axis_index.
@@ -574,17 +579,23 @@ class Experiment_VDM(Experiment):
         'dpm2m' (mulan_amd.sampling) over T uniform steps or the explicit t_grid (1 -> 0, strictly decreasing: it sets
         the step count); generate_x then draws with rng.fold_in(N) like the ancestral loop with fold_in(T).
         'sde2m' (SDE-DPM-Solver++(2M)) and 'ddim' with eta in (0, 1] are the stochastic few-step samplers: step k draws
-        its noise under the key the ancestral loop folds with its step index (rng.fold_in(k) after the split below)."""
+        its noise under the key the ancestral loop folds with its step index (rng.fold_in(k) after the split below).
+        grid, grid_rho: the kind of time grid of a few-step sampler (sampling.GRIDS; 'logsnr' and 'karras' are spaced
+        on the mean schedule of the batch, model.fast_grid) -- over T steps, so not together with t_grid."""
         sampling.check_eta(sampler, eta)
         if sampler == 'ancestral' and t_grid is not None:
             raise ValueError("t_grid applies to the few-step samplers; the ancestral sampler runs T uniform steps")
-        grid = None if sampler == 'ancestral' else sampling.time_grid(None if t_grid is not None else T, t_grid)
+        kind, grid_rho = sampling.check_grid(sampler, grid, t_grid, grid_rho)
+        grid = None                                  # (a grid kind other than 'uniform' is made per batch, in fast_sample)
+        if sampler != 'ancestral' and kind == 'uniform':
+            grid = sampling.time_grid(None if t_grid is not None else T, t_grid)
         N = T if grid is None else len(grid) - 1
         rng = rng.fold_in(self.rank)
         B = dummy_inputs.shape[0]
         rng, sample_rng = rng.split()
         samples, _ = self.draw_samples(params, B, None, sample_rng, rng, rng.fold_in(N), sampler, N, t_grid=grid,
-                                       prior_scale=float(self.config.model.sigma_prior), eta=eta)
+                                       prior_scale=float(self.config.model.sigma_prior), eta=eta, grid=kind,
+                                       grid_rho=grid_rho)
         return parallel.all_gather_tensor(samples) if gather else samples
 
     def _packer_for(self, params):
@@ -596,7 +607,7 @@ class Experiment_VDM(Experiment):
 
     def draw_samples(self, params, B, embedding, prior_rng, step_rng, decode_rng, sampler, steps, t_grid=None,
                      prior_scale=1.0, stepper=None, eta=0.0, known=None, mask=None, resample=1, known_rng=None,
-                     measurement=None, degradation=None):
+                     measurement=None, degradation=None, grid='uniform', grid_rho=7.0):
         """One batch of B images, the loop every sampling entry point runs: z_1 = prior_scale * N(0, I) from prior_rng,
         `steps` steps of `sampler` under `embedding` (MuLAN models; None: model.deterministic_embedding) with the per-step
         noise of the ancestral sampler from step_rng (rng.fold_in(i) at step i), generate_x with decode_rng (needed by
@@ -613,9 +624,12 @@ class Experiment_VDM(Experiment):
         degradation ('sr:f', 'gray', 'sr:f+gray'): restoration with the few-step samplers instead (sampling.run):
         every step's prediction is projected onto the measurement.  resample > 1 draws jump j under known_rng.fold_in(j);
         resample = 1 draws nothing from known_rng and needs none.  A mask and a measurement in one run are refused.
+        grid, grid_rho: the kind of time grid of a few-step sampler (sampling.GRIDS; not with t_grid); 'logsnr' and
+        'karras' are spaced on the mean schedule of this batch's embeddings (model.fast_grid).
         -> (uint8 [B, 32, 32, 3], stepper or None)"""
         step_eta = sampling.check_eta(sampler, eta)          # what the steps run with: 1 for sde2m
         inpaint, restore, resample = sampling.check_guidance(sampler, known, mask, measurement, degradation, resample)
+        grid, grid_rho = sampling.check_grid(sampler, grid, t_grid, grid_rho)
         if restore is not None:
             if resample > 1 and known_rng is None:
                 raise ValueError("draw_samples: resample > 1 needs known_rng, the key of the jumps' noise")
@@ -667,7 +681,7 @@ class Experiment_VDM(Experiment):
                         kw.update(resample=resample, known_noise=known_rng)
                     z = self.model.fast_sample(params, z, ctx, sampler, None if t_grid is not None else steps, t_grid,
                                                stepper=stepper, eta=eta, noise=step_rng if step_eta > 0.0 else None,
-                                               **kw)
+                                               grid=grid, grid_rho=grid_rho, **kw)
                     coeffs = ctx.get("coeffs")
                 samples = self.model.generate_x(params, z, coeffs, rng=decode_rng)
             finally:

@@ -788,11 +788,29 @@ class _VDMBase:
                                  lambda: EagerFastStep(self, params, B, device, ctx, step_eta, inpaint, restore),
                                  "HIP-graph capture of the few-step sampler's step failed (%s: %s); sampling eagerly")
 
+    def schedule_ends(self, params, ctx):
+        """-> (gamma_bar(0), gamma_bar(1)) of the batch's mean schedule, as floats"""
+        raise NotImplementedError
+
+    def schedule_times(self, params, ctx, targets):
+        """-> fp32 [M] on the device: the times in [0, 1] at which the batch's mean schedule gamma_bar takes the values
+        `targets` (float64 [M]); what the 'logsnr' and 'karras' grids of the few-step samplers are made of
+        (sampling.make_grid)"""
+        raise NotImplementedError
+
+    def fast_grid(self, params, ctx, steps=None, t_grid=None, grid="uniform", grid_rho=7.0):
+        """-> the time grid of a few-step run on this batch (sampling.make_grid): float64 [N + 1].  A 'logsnr' or
+        'karras' grid costs schedule_times on the batch's context and one read of N - 1 floats"""
+        from . import sampling
+        return sampling.make_grid(grid, steps, t_grid, grid_rho, lambda: self.schedule_ends(params, ctx),
+                                  lambda targets: self.schedule_times(params, ctx, targets))
+
     def fast_sample(self, params, z, ctx, sampler="dpm2m", steps=None, t_grid=None, graph=None, stepper=None, eta=0.0,
                     noise=None, known=None, mask=None, resample=1, known_noise=None, measurement=None,
-                    degradation=None):
-        """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m | sde2m) over `steps` uniform steps or the explicit
-        t_grid; stepper: one from fast_stepper to re-use (its set_context re-targets it at this batch's ctx).
+                    degradation=None, grid="uniform", grid_rho=7.0):
+        """z_0 from z_1 = z [B, 3072] by `sampler` (ddim | dpm2m | sde2m) over `steps` steps on the grid kind `grid`
+        (sampling.GRIDS; 'uniform': uniform in t; 'logsnr' and 'karras', with grid_rho, are spaced on the mean schedule
+        of this batch: fast_grid) or the explicit t_grid; stepper: one from fast_stepper to re-use (its set_context re-targets it at this batch's ctx).
         eta: for ddim (0: the deterministic sampler).  noise (sde2m, ddim with eta > 0): the batch's step key -- step k
         draws xi = randn under noise.fold_in(k) -- or a callable k -> xi [B, 3072].
         known (fp32 [B, 3072], the image as ops.encode_u8 gives it) and mask (uint8 or bool [B, 3072], non-zero = keep):
@@ -807,6 +825,7 @@ class _VDMBase:
         from . import sampling
         step_eta = sampling.check_eta(sampler, eta)
         inpaint, restore, resample = sampling.check_guidance(sampler, known, mask, measurement, degradation, resample)
+        grid, grid_rho = sampling.check_grid(sampler, grid, t_grid, grid_rho)
         B = z.shape[0]
         if restore is not None:
             shape = ops.restore_y_shape(B, *HWC, *restore)
@@ -824,7 +843,8 @@ class _VDMBase:
                 raise ValueError(f"fast_sample: mask is uint8 or bool [{B}, {D}]; got {mask.dtype} {tuple(mask.shape)}")
             if known_noise is None:
                 raise ValueError("fast_sample: inpainting needs `known_noise` (the batch's known-region key)")
-        grid = sampling.time_grid(steps, t_grid)
+        with torch.no_grad():
+            grid = self.fast_grid(params, ctx, steps, t_grid, grid, grid_rho)
         orders = sampling.step_orders(sampler, len(grid) - 1)
         if step_eta > 0.0 and noise is None:
             raise ValueError(f"fast_sample: {sampler!r} with eta = {step_eta} is stochastic and needs `noise`")
@@ -1014,6 +1034,16 @@ class MulanVDM(_VDMBase):
         return dict(emb=embedding.contiguous(), cond=conditioning.reshape(B, 1).to(torch.float32).contiguous(),
                     coeffs=tuple(coeffs))
 
+    def schedule_ends(self, params, ctx):
+        """the fixed end points of the polynomial schedule: every sub-pixel's, so the mean's"""
+        return float(self.config.gamma_min), float(self.config.gamma_max)
+
+    def schedule_times(self, params, ctx, targets):
+        """the mean over the batch's sub-pixels of the polynomial schedule is a quintic in t: its five coefficients by
+        ops.schedule_moments on the batch's coefficients, its roots by ops.schedule_invert"""
+        cfg = self.config
+        return ops.schedule_invert(ops.schedule_moments(*ctx["coeffs"]), targets, cfg.gamma_min, cfg.gamma_max)
+
     def _ode_gamma(self, params, ctx, t):
         cfg = self.config
         _, _, gt, gp = ops.poly_gamma(*ctx["coeffs"], t, cfg.gamma_min, cfg.gamma_max)
@@ -1200,6 +1230,18 @@ class PlainVDM(_VDMBase):
 
     def _fast_gamma(self, params, ctx, t):
         return self._gamma(params, t)[0].contiguous()
+
+    def schedule_ends(self, params, ctx):
+        g = self._gamma(params, torch.tensor([0.0, 1.0], device=ctx["cond"].device))[0]
+        return tuple(float(v) for v in g.tolist())
+
+    def schedule_times(self, params, ctx, targets):
+        """the scalar schedule gamma(t) is every sample's, so the mean's: all targets at once by bisection on [0, 1]
+        through _gamma, 32 halvings in fp32 (sampling.bisect_times) -- exact up to fp32 for the linear schedules.  A
+        handful of elementwise operations on [M] values per halving: no kernel of its own is needed here"""
+        from . import sampling
+        tg = torch.as_tensor(targets, dtype=torch.float32).reshape(-1).to(ctx["cond"].device)
+        return sampling.bisect_times(lambda t: self._gamma(params, t)[0], tg)
 
     def _fast_gamma_shape(self, B):
         return (B,)

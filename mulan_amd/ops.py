@@ -2285,6 +2285,34 @@ def rowmean(x):
     return out
 
 
+def schedule_moments(a, b, c):
+    """fp32 [B, 5]: per sample the means over its 3072 sub-pixels of (c^2, b c, (b^2 + 2 a c) / 3, a b / 2, a^2 / 5) / S,
+    the coefficients of t .. t^5 in the sample's mean schedule (gamma_bar - gamma_min) / (gamma_max - gamma_min)
+    (mulan_schedule_moments); a, b, c fp32 [B, 3072], the coefficients of the polynomial schedule"""
+    a, b, c = _c(a), _c(b), _c(c)
+    if not (a.dtype == b.dtype == c.dtype == torch.float32) or a.dim() != 2 or a.shape[1] != D \
+            or b.shape != a.shape or c.shape != a.shape:
+        raise ValueError(f"schedule_moments: a, b, c are fp32 [B, {D}]; got {[tuple(x.shape) for x in (a, b, c)]}")
+    m = torch.empty((a.shape[0], 5), device=a.device, dtype=torch.float32)
+    call("mulan_schedule_moments", ptr(a), ptr(b), ptr(c), a.shape[0], D, ptr(m), stream())
+    return m
+
+
+def schedule_invert(m, targets, gmin, gmax):
+    """fp32 [M]: the times t in [0, 1] at which the mean schedule of the batch, gamma_bar(t) = gmin + (gmax - gmin)
+    sum_k mean_b(m[b, k]) t^(k + 1), takes the values `targets` (float64 [M], any array or tensor; a target >= gmax
+    gives exactly 1, one <= gmin exactly 0); m fp32 [B, 5] from schedule_moments (mulan_schedule_invert)"""
+    m = _c(m)
+    if m.dtype != torch.float32 or m.dim() != 2 or m.shape[1] != 5 or m.shape[0] < 1:
+        raise ValueError(f"schedule_invert: m is fp32 [B, 5]; got {m.dtype} {tuple(m.shape)}")
+    tg = torch.as_tensor(targets, dtype=torch.float64).reshape(-1).to(m.device).contiguous()
+    if tg.numel() < 1:
+        raise ValueError("schedule_invert: no target")
+    out = torch.empty(tg.numel(), device=m.device, dtype=torch.float32)
+    call("mulan_schedule_invert", ptr(m), m.shape[0], ptr(tg), tg.numel(), float(gmin), float(gmax), ptr(out), stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- exact-likelihood ODE (eval only)
 def topk_hard(logits, k):
     """(k-hot embedding of the plain logits, KL(softmax(logits) || uniform)): notebook_utils.logits_to_embeddings and

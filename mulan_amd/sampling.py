@@ -29,6 +29,12 @@ a data prediction (mode 2 of the same step kernels); the multistep history is x_
 space, so the different schedules inside a group do not enter.  resample = U > 1 is DDNM's time travel: U - 1 rounds of
 jump and first-order step after every step but the last.
 
+Time grids (make_grid; the keyword `grid`): uniform in t (the default), quadratic in t, or spaced on the mean schedule
+of the batch -- uniform in its log signal-to-noise ratio ('logsnr') or the EDM grid ('karras').  The mean of the
+polynomial schedules of a batch is a quintic in t, whose five coefficients and roots two HIP kernels give
+(ops.schedule_moments, ops.schedule_invert; model.schedule_times); the times are read back once per batch and go
+through time_grid's checks like an explicit t_grid, so the steppers never see which kind a grid was.
+
 One loop (run) and one step body (solver_step) serve the plain, the inpainting and the restoring run, for the stepper of
 this module and for the models' replayed one; check_guidance is the one place that decides which of the three a run is.
 """
@@ -85,6 +91,98 @@ def time_grid(steps=None, t_grid=None):
     if steps is not None and steps != g.size - 1:
         raise ValueError(f"steps = {steps} but t_grid has {g.size - 1} steps")
     return g
+
+
+GRIDS = ("uniform", "logsnr", "karras", "quadratic")
+HOST_GRIDS = ("uniform", "quadratic")       # grids that need no schedule: the others invert the batch's mean schedule
+BISECT_HALVINGS = 32
+
+
+def check_grid(sampler, grid="uniform", t_grid=None, rho=7.0):
+    """the public keywords `grid` and `grid_rho` of a sampler -> (grid, rho): the kind is one of GRIDS, anything but
+    'uniform' excludes an explicit t_grid and the ancestral sampler, and rho (karras) is finite and > 0"""
+    check_sampler(sampler)
+    if grid not in GRIDS:
+        raise ValueError(f"unknown grid {grid!r} (one of {', '.join(GRIDS)})")
+    try:
+        rho = float(rho)
+    except (TypeError, ValueError):
+        raise ValueError(f"grid_rho must be a finite number > 0, got {rho!r}") from None
+    if not (np.isfinite(rho) and rho > 0.0):
+        raise ValueError(f"grid_rho must be a finite number > 0, got {rho!r}")
+    if grid != "uniform":
+        if t_grid is not None:
+            raise ValueError(f"grid = {grid!r} and an explicit t_grid both name the times: pass t_grid alone "
+                             "(grid = 'uniform'), or drop it")
+        if sampler not in FAST_SAMPLERS:
+            raise ValueError(f"grid = {grid!r} belongs to the few-step samplers ({', '.join(FAST_SAMPLERS)}); the "
+                             f"{sampler!r} sampler steps on its own T uniform times: use grid = 'uniform'")
+    return grid, rho
+
+
+def check_steps(steps):
+    if steps is None or int(steps) != steps or steps < 1:
+        raise ValueError(f"the number of sampling steps must be an integer >= 1, got {steps!r}")
+    return int(steps)
+
+
+def grid_targets(grid, steps, g0, g1, rho=7.0):
+    """-> float64 [N - 1]: the values gamma_bar takes at the interior times t_1 .. t_{N-1} of a 'logsnr' or 'karras'
+    grid, g0 = gamma_bar(0) and g1 = gamma_bar(1) its ends.  logsnr: linear in i from g1 to g0.  karras: with
+    sigma / alpha = exp(gamma / 2), (sigma / alpha)^(1 / rho) is linear in i between its end values (the EDM grid)"""
+    N = check_steps(steps)
+    g0, g1 = float(g0), float(g1)
+    w = np.arange(1, N, dtype=np.float64) / N
+    if grid == "logsnr":
+        return g1 + (g0 - g1) * w
+    if grid == "karras":
+        r1, r0 = np.exp(g1 / (2.0 * rho)), np.exp(g0 / (2.0 * rho))
+        return 2.0 * rho * np.log(r1 + (r0 - r1) * w)
+    raise ValueError(f"grid {grid!r} has no targets: it needs no schedule")
+
+
+def bisect_times(gamma_fn, targets, halvings=BISECT_HALVINGS):
+    """-> the times t in [0, 1] with gamma_fn(t) = targets, for an increasing gamma_fn that maps a tensor of times to
+    the tensor of its values: all targets at once, `halvings` halvings of [0, 1], in the dtype and on the device of
+    `targets` (a torch tensor).  A target at or beyond an end value gives that end exactly"""
+    lo, hi = torch.zeros_like(targets), torch.ones_like(targets)
+    g_lo, g_hi = gamma_fn(lo), gamma_fn(hi)
+    for _ in range(halvings):
+        mid = 0.5 * (lo + hi)
+        below = gamma_fn(mid) < targets
+        lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+    t = 0.5 * (lo + hi)
+    t = torch.where(targets >= g_hi, torch.ones_like(t), t)
+    return torch.where(targets <= g_lo, torch.zeros_like(t), t)
+
+
+def make_grid(grid="uniform", steps=None, t_grid=None, rho=7.0, ends_fn=None, times_fn=None):
+    """-> float64 [N + 1] from 1 to 0, through time_grid's checks: the grid kind `grid` over `steps` steps (or, with
+    'uniform', the explicit t_grid).
+      uniform ..... t_i = 1 - i / N (time_grid, as without the keyword)
+      quadratic ... t_i = (1 - i / N)^2
+      logsnr ...... gamma_bar(t_i) linear in i: uniform in the log signal-to-noise ratio of the mean schedule
+      karras ...... (sigma / alpha)^(1 / rho) of the mean schedule linear in i
+    The last two take the schedule from the caller: ends_fn() -> (gamma_bar(0), gamma_bar(1)) and times_fn(targets
+    float64 [N - 1]) -> the times there, as fp32 values (array or tensor; read back here, once).  t_0 = 1 and t_N = 0
+    are set here."""
+    if grid == "uniform":
+        return time_grid(steps, t_grid)
+    N = check_steps(steps)
+    if grid == "quadratic":
+        return time_grid(N, (1.0 - np.arange(N + 1, dtype=np.float64) / N) ** 2)
+    if ends_fn is None or times_fn is None:
+        raise ValueError(f"grid = {grid!r} needs the schedule (its end values and its inverse)")
+    inner = np.zeros(0)
+    if N > 1:
+        g0, g1 = ends_fn()
+        inner = times_fn(grid_targets(grid, N, g0, g1, rho))
+        inner = (inner.detach().cpu().numpy() if torch.is_tensor(inner) else np.asarray(inner)).astype(np.float64)
+    try:
+        return time_grid(N, np.concatenate([[1.0], inner.reshape(-1), [0.0]]))
+    except ValueError as e:
+        raise ValueError(f"the {grid!r} grid of {N} steps is no time grid on this schedule ({e}): use fewer steps or "
+                         "another grid") from None
 
 
 def step_orders(sampler, steps):
@@ -377,7 +475,8 @@ def run(stepper, z, grid, orders, resample=1, known=None, mask=None, known_noise
 
 
 def sample(net_fn, gamma_fn, z, mode, sampler="dpm2m", steps=None, t_grid=None, eta=0.0, noise_fn=None, known=None,
-           mask=None, known_noise_fn=None, resample=1, measurement=None, degradation=None, hwc=None):
+           mask=None, known_noise_fn=None, resample=1, measurement=None, degradation=None, hwc=None, grid="uniform",
+           grid_rho=7.0, gamma_bar_fn=None):
     """z_0 from z_1 = z by `sampler` (ddim | dpm2m | sde2m) over `steps` uniform steps or the explicit `t_grid`; mode as
     ops.fast_sampler_step (0: net_fn gives the velocity, 1: eps_hat, 2: x_hat).  eta (ddim only): 0 is the
     deterministic sampler; sde2m and ddim with eta > 0 need noise_fn(k) -> xi shaped like z, the noise of step k.
@@ -385,10 +484,22 @@ def sample(net_fn, gamma_fn, z, mode, sampler="dpm2m", steps=None, t_grid=None, 
     with `resample` passes per step, on known_noise_fn(j) -> xi shaped like z (run states which j is drawn when).
     measurement, degradation (a spec of parse_degradation, or its pair): restoration instead, the measurement fp32
     shaped ops.restore_y_shape in the scale of ops.encode_u8; z is [B, H, W, C] or hwc names (H, W, C); `resample`
-    passes per step on known_noise_fn(j), the noise of jump j (run)"""
+    passes per step on known_noise_fn(j), the noise of jump j (run).
+    grid (one of GRIDS; make_grid) with grid_rho for 'karras': 'logsnr' and 'karras' space the steps on the mean
+    schedule, which gamma_fn does not give: gamma_bar_fn(t float64 array [M]) -> gamma_bar there (array or tensor),
+    increasing in t; its inverse is taken here by bisection on the host in float64 (bisect_times)"""
     step_eta = check_eta(sampler, eta)
     check_guidance(sampler, known, mask, measurement, degradation, resample)
-    grid = time_grid(steps, t_grid)
+    grid, grid_rho = check_grid(sampler, grid, t_grid, grid_rho)
+    if grid not in HOST_GRIDS and gamma_bar_fn is None:
+        raise ValueError(f"grid = {grid!r} is spaced on the mean schedule: pass gamma_bar_fn(t) -> gamma_bar, or use "
+                         f"one of {', '.join(HOST_GRIDS)}")
+
+    def gamma_bar(t):
+        g = gamma_bar_fn(t.numpy())
+        return (g.detach().cpu() if torch.is_tensor(g) else torch.as_tensor(np.asarray(g))).to(torch.float64).reshape(-1)
+    grid = make_grid(grid, steps, t_grid, grid_rho, lambda: gamma_bar(torch.tensor([0.0, 1.0], dtype=torch.float64)).tolist(),
+                     lambda targets: bisect_times(gamma_bar, torch.as_tensor(targets), 60).numpy().astype(np.float32))
     orders = step_orders(sampler, len(grid) - 1)
     with torch.no_grad():
         return run(EagerStepper(net_fn, gamma_fn, mode, step_eta, noise_fn, known, mask, known_noise_fn, measurement,

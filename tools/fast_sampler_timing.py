@@ -5,12 +5,14 @@ does not depend on them).  Forms, alternated within one run after one untimed wa
   with --inpaint also dpm2m N = 25 replayed under a half:left mask at resample 1 (25 network evaluations, one mix per
   step) and at resample 2 (49 evaluations, a jump and a mix more per repeated step);
   with --restore also dpm2m N = 25 replayed under an sr:4 measurement at resample 1 (25 evaluations, one projection per
-  step).
+  step);
+  with --grid KIND also dpm2m N = 25 replayed on that time grid (logsnr | karras | quadratic; the first two add two
+  small launches and one read of 24 floats per batch: ops.schedule_moments, ops.schedule_invert).
 Each time is one batch from z_1 to the uint8 images (the loop plus generate_x) with the stepper built beforehand (what
 `python -m ldm.sample` pays per batch), between two device synchronisations.  One JSON line per timed batch, then a
 summary line (median ms per batch).
 
-    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3] [--few-step-only] [--inpaint] [--restore]
+    python tools/fast_sampler_timing.py [--batch 64] [--rounds 3] [--few-step-only] [--inpaint] [--restore] [--grid logsnr]
 """
 import argparse
 import json
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--few-step-only", action="store_true", help="leave the 1000-step ancestral form out")
     ap.add_argument("--inpaint", action="store_true", help="add dpm2m with a mask at resample 1 and 2")
     ap.add_argument("--restore", action="store_true", help="add dpm2m with an sr:4 measurement at resample 1")
+    ap.add_argument("--grid", default=None, help="add dpm2m on this time grid (logsnr, karras or quadratic)")
     args = ap.parse_args()
     import torch
     from mulan_amd.config import load_config_file
@@ -91,6 +94,9 @@ def main():
         y = ops.restore_measure(ops.encode_u8(torch.randint(0, 256, (B, 32, 32, 3), dtype=torch.uint8, device=dev)), 4, False)
         forms += [("dpm2m_N25_restore_sr4_replayed", lambda: model.generate_x(params, model.fast_sample(
             params, z1, ctx, "dpm2m", 25, stepper=restore_replay, measurement=y, degradation="sr:4"), ctx["coeffs"]))]
+    if args.grid is not None:
+        forms += [(f"dpm2m_N25_{args.grid}_replayed", lambda: model.generate_x(params, model.fast_sample(
+            params, z1, ctx, "dpm2m", 25, stepper=fast_replay, grid=args.grid), ctx["coeffs"]))]
     if args.few_step_only:
         forms = forms[1:]
     times = {name: [] for name, _ in forms}
