@@ -83,24 +83,15 @@ size_t mulan_conv3x3_wgrad_workspace(int B, int H, int W, int C, int N);
 int mulan_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* workspace, int B, int H, int W, int C,
                         int N, int accumulate, mulan_stream_t stream);
 
-/* fp32-equivalent fast path on the bf16 matrix cores (6-pass split, = XLA's float32 / HIGHEST matmul precision that
- * the reference requests in ldm/main.py:39).  wp = weights pre-split by mulan_conv3x3_pack_bf16x6 (flip = 1 packs the
- * tap-flipped, channel-transposed weights of the input-gradient convolution).  Needs C % 16 == 0 and N % 128 == 0. */
-size_t mulan_conv3x3_pack_bf16x6_bytes(int C, int N);
-int mulan_conv3x3_pack_bf16x6(const float* w, void* wp, int C, int N, int flip, mulan_stream_t stream);
-int mulan_conv3x3_fwd_bf16x6(const float* x, const void* wp, const float* bias, const float* cbias, int cbias_mode,
-                             const float* res, float* y, int B, int H, int W, int C, int N, mulan_stream_t stream);
-
-size_t mulan_conv3x3_wgrad_bf16x6_workspace(int B, int H, int W, int C, int N);
-int mulan_conv3x3_wgrad_bf16x6(const float* x, const float* dy, float* dw, float* workspace, int B, int H, int W,
-                               int C, int N, int accumulate, mulan_stream_t stream);
-
 /* fp32-equivalent fast path on the fp16 matrix cores (3-pass split of power-of-two-scaled operands into two fp16
- * pieces each; same contract as above at half the matrix-core cycles).  mulan_absmax_rows gives the per-image
+ * pieces each; the same contract as mulan_conv3x3_fwd at the float32 / HIGHEST matmul precision the reference requests
+ * in ldm/main.py:39).  mulan_absmax_rows gives the per-image
  * maxima from which the kernels derive the operand scales: out[r][0..15] = fp32 bit patterns of 16 partial maxima of
  * |x[r, 0:row_len]| (consumers take the maximum of a row's 16 entries; no atomics, no zero-fill pass).
- * wmax[16] = mulan_absmax_rows(w, 1 row); wp from mulan_conv3x3_pack_f16x3 (flip as above).
- * Needs C % 16 == 0 and N % 128 == 0. */
+ * wmax[16] = mulan_absmax_rows(w, 1 row); wp = weights pre-split by mulan_conv3x3_pack_f16x3 (flip = 1 packs the
+ * tap-flipped, channel-transposed weights of the input-gradient convolution).
+ * mulan_conv3x3_fwd_f16x3 and mulan_conv3x3_fwd_f16x3_alone need H % 8 == 0, C % 16 == 0 and N % 128 == 0 (the
+ * kernels tile the image in blocks of 8 rows; anything else returns an error and launches nothing). */
 int mulan_absmax_rows(const float* x, unsigned* out, int rows, size_t row_len, mulan_stream_t stream);
 /* c = a + b (c may alias a or b) with out = mulan_absmax_rows(c) in the same pass: the gradient sum autograd forms for
  * a tensor with two consumers (the U-Net skip connections, model_vdm.py:351-372) fused with the maxima pass of the

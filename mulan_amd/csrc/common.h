@@ -35,7 +35,8 @@ __device__ __forceinline__ f32x4 ld_stream4(const float* p) {
 
 // developer tuning knobs (mulan_set_tuning): [0] conv fwd variant, [1] wgrad resident-block target; the other words are
 // documented where they are read.  Words 4, 6, 7, 18 and 29 selected kernel variants that were retired (DESIGN.md
-// section 3.2): they are still accepted and have no reader.
+// section 3.2): they are still accepted and have no reader.  Word 3 forces the 8-row 32x32x16 f16x3 convolution kernel
+// when it is non-zero (2 by convention; the value 1 once selected a 4-row kernel that was retired).
 extern int g_mulan_tune[32];
 extern unsigned long long* g_mulan_debug_buffer;   // dev-only stamp buffer (>= 64 u64), normally null
 

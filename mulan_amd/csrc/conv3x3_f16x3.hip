@@ -5,17 +5,19 @@
 // |v s - h - l| <= 2^-24 |v s| as long as l is a normal fp16 number, and <= 2^-25 absolute below that: fp16 subnormals
 // are honoured by the matrix cores, tools/f16_probe.hip), and
 //     a * b  ~=  a_h b_h + a_h b_l + a_l b_h                    (the dropped a_l b_l is <= 2^-24 |a b|)
-// is accumulated in fp32 by three v_mfma_f32_32x32x16_f16 per 16-deep k step: half the matrix-pipe cycles of the
-// 6-pass bf16 split (conv3x3_bf16x6.hip) and 5.3x fewer than v_mfma_f32_32x32x2_f32, at the same measured error
-// against fp64 as either (tools/f16_probe.hip, tests/test_gpu_f16x3.py).  The power-of-two scales are exact and
-// are divided out of the fp32 accumulators in the epilogue.  Activations / output gradients carry one scale per
+// is accumulated in fp32 by three v_mfma_f32_32x32x16_f16 per 16-deep k step: 5.3x fewer matrix-pipe cycles than
+// v_mfma_f32_32x32x2_f32 at the same measured error against fp64 (tools/f16_probe.hip, tests/test_gpu_f16x3.py), and
+// half the cycles of the 6-pass split into three bf16 pieces that the project used before.  The power-of-two scales
+// are exact and are divided out of the fp32 accumulators in the epilogue.  Activations / output gradients carry one scale per
 // image (every image is normalised on its own, so images of very different magnitude in one batch keep full
 // precision); weights carry one scale per tensor; the weight-gradient kernel, which sums over images, uses the
 // per-tensor maxima.  The reference asks XLA for float32 matmul precision (ldm/main.py:39); this is that contract.
 //
-// Tiling is the one of conv3x3_bf16x6_kernel: block = 4 image rows x 128 couts, wave = 2 rows x 64 couts, halo patch
-// in LDS, one stage per (16-channel chunk, tap), weights pre-split by mulan_conv3x3_pack_f16x3 into the LDS tile
-// layout [cout][plane][16 k], 3-deep weight ring.
+// Forward / input-gradient tiling: a block covers 8 image rows x 128 couts of one image, with the halo patch of its rows
+// in LDS and one stage per (16-channel chunk, tap); the weights are pre-split by mulan_conv3x3_pack_f16x3 into tiles
+// [tap][chunk][cout][plane][16 k] that a wave's MFMA operand reads directly.  Two kernels share it: the 32x32x16
+// one-block-per-CU kernel below and the 16x16x32 two-blocks-per-CU kernel of conv3x3_f16x3_v3.hip (the default where
+// C % 32 == 0).
 #include "common.h"
 #include "f16x3_common.h"
 
@@ -23,236 +25,12 @@ namespace {
 
 using namespace f16x3;
 
-__global__ __launch_bounds__(256) void conv3x3_f16x3_kernel(ConvArgsH p) {
-  constexpr int MT = 2, NT = 2, WN = 2;
-  constexpr int PV = 4;                          // float4 patch slots per thread (816 slots)
-  constexpr int WV = 2;                          // 16-byte weight pieces per thread (512 pieces)
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* pbuf0 = smem;
-  unsigned char* wbuf0 = smem + PATCH_B;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int wm = wave / WN, wn = wave % WN;
-  const int tiles_per_img = p.H / TROWS;
-  const int b = blockIdx.x / tiles_per_img;
-  const int h0 = (blockIdx.x % tiles_per_img) * TROWS;
-  const int n0 = blockIdx.y * BN;
-  const int C = p.C, N = p.N;
-  const int nchunks = C / CK;
-  const float* xb = p.x + (size_t)b * p.H * kW * C;
-  float sx, inv_x, sw, inv_w;
-  scale_of(row_max16(p.xmax, b), sx, inv_x);
-  scale_of(row_max16(p.wmax, 0), sw, inv_w);
-
-  f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // chunk / stage invariant prefetch addressing
-  const float* pptr[PV];
-  int pdst[PV];
-  unsigned phalo = 0;
-#pragma unroll
-  for (int s = 0; s < PV; ++s) {
-    const int slot = tid + s * 256;
-    const int q = slot & 3, pix = slot >> 2;
-    const int prow = pix / kPW, pcol = pix - prow * kPW;
-    const int hh = h0 + prow - 1, ww = pcol - 1;
-    const bool inb = slot < (TROWS + 2) * kPW * 4;
-    const bool ok = inb && hh >= 0 && hh < p.H && ww >= 0 && ww < kW;
-    pptr[s] = ok ? xb + ((size_t)hh * kW + ww) * C + q * 4 : p.x;
-    pdst[s] = inb ? pix * PIXB + q * 8 : -1;
-    phalo |= (ok ? 1u : 0u) << s;
-  }
-  int wsrc[WV], wdst[WV];
-#pragma unroll
-  for (int s = 0; s < WV; ++s) {
-    const int part = tid + s * 256;              // 16-byte piece of the 128 x 64 B tile
-    const int n = part >> 2, piece = part & 3;
-    wsrc[s] = part * 16;
-    wdst[s] = n * NB + piece * 16;
-  }
-  const size_t tile_stride = (size_t)N * 64;     // bytes between (tap, chunk) tiles of the packed weights
-  const unsigned char* wtile0 = p.wp + (size_t)n0 * 64;
-
-  f32x4 preg[PV];
-  f32x4 wreg[WV];
-  auto gload_patch = [&](int cc) {
-#pragma unroll
-    for (int s = 0; s < PV; ++s) preg[s] = *reinterpret_cast<const f32x4*>(pptr[s] + (((phalo >> s) & 1u) ? cc * CK : 0));
-  };
-  auto store_patch = [&](unsigned char* pb) {
-#pragma unroll
-    for (int s = 0; s < PV; ++s) {
-      if (pdst[s] < 0) continue;
-      f32x4 v = preg[s];
-      if (!((phalo >> s) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};
-      f16x4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        _Float16 h, l;
-        split2(v[e] * sx, h, l);
-        hi[e] = h; lo[e] = l;
-      }
-      *reinterpret_cast<f16x4*>(pb + pdst[s]) = hi;
-      *reinterpret_cast<f16x4*>(pb + pdst[s] + 32) = lo;
-    }
-  };
-  auto gload_w = [&](int cc, int tap) {
-    const unsigned char* t = wtile0 + ((size_t)tap * nchunks + cc) * tile_stride;
-#pragma unroll
-    for (int s = 0; s < WV; ++s) wreg[s] = *reinterpret_cast<const f32x4*>(t + wsrc[s]);
-  };
-  auto store_w = [&](unsigned char* wb) {
-#pragma unroll
-    for (int s = 0; s < WV; ++s) *reinterpret_cast<f32x4*>(wb + wdst[s]) = wreg[s];
-  };
-
-  // Software pipeline: see conv3x3_bf16x6_kernel.  Tile s+1 is complete while stage s computes, so stage s+1's
-  // fragments are read from LDS during stage s's 12 MFMAs; tile s+2 is fetched from L2 meanwhile.
-  const int nsteps = nchunks * 9;
-  auto tile_of = [&](int s2, int& cc2, int& tap2) { cc2 = s2 / 9; tap2 = s2 - cc2 * 9; };
-  auto read_frags = [&](f16x8 (&af)[MT][2], f16x8 (&bfr)[NT][2], int tap, const unsigned char* wb) {
-    const int kh = tap / 3, kw = tap - kh * 3;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int prow = wm * MT + mt + kh, pcol = li + kw;
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl)
-        af[mt][pl] = *reinterpret_cast<const f16x8*>(pbuf0 + (prow * kPW + pcol) * PIXB + pl * 32 + lh * 16);
-    }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl)
-        bfr[nt][pl] = *reinterpret_cast<const f16x8*>(wb + ((wn * NT + nt) * 32 + li) * NB + pl * 32 + lh * 16);
-  };
-
-  const bool stamp = p.stamps && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
-  if (stamp) { p.stamps[0] = __builtin_amdgcn_s_memtime(); p.stamps[30] = __builtin_amdgcn_s_memrealtime(); }
-  gload_patch(0);
-  gload_w(0, 0);
-  store_patch(pbuf0);
-  store_w(wbuf0);
-  if (nsteps > 1) {
-    gload_w(0, 1);
-    store_w(wbuf0 + WT_B);
-  }
-  __syncthreads();
-
-  f16x8 afc[MT][2], bfc[NT][2], afn[MT][2], bfn[NT][2];
-  read_frags(afc, bfc, 0, wbuf0);
-  int step = 0, slot_next = 1, slot_fill = 2;          // ring slots of tile step+1 / step+2
-  if (stamp) p.stamps[1] = __builtin_amdgcn_s_memtime();
-  for (int cc = 0; cc < nchunks; ++cc) {
-    if (stamp && cc < 20) p.stamps[2 + cc] = __builtin_amdgcn_s_memtime();
-    const bool more_chunks = cc + 1 < nchunks;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap, ++step) {
-      const bool has_next = step + 1 < nsteps, has_fill = step + 2 < nsteps;
-      if (tap < 8) read_frags(afn, bfn, tap + 1, wbuf0 + slot_next * WT_B);   // next stage's operands, same patch
-      if (has_fill) {
-        int c2, t2;
-        tile_of(step + 2, c2, t2);
-        gload_w(c2, t2);
-      }
-      if (tap == 0 && more_chunks) gload_patch(cc + 1);
-      __builtin_amdgcn_sched_barrier(0);
-
-      // small terms first: a_l b_h, a_h b_l, a_h b_h
-#pragma unroll
-      for (int term = 0; term < 3; ++term) {
-        constexpr int PA[3] = {1, 0, 0};
-        constexpr int PB[3] = {0, 1, 0};
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt)
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afc[mt][PA[term]], bfc[nt][PB[term]], acc[mt][nt], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (has_fill) store_w(wbuf0 + slot_fill * WT_B);
-      __syncthreads();
-      if (tap == 8 && more_chunks) {       // every wave has left this chunk's patch: replace it
-        store_patch(pbuf0);
-        __syncthreads();
-      }
-      if (tap == 8 && has_next) read_frags(afn, bfn, 0, wbuf0 + slot_next * WT_B);
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) afc[mt][pl] = afn[mt][pl];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) bfc[nt][pl] = bfn[nt][pl];
-      slot_next = slot_next == 2 ? 0 : slot_next + 1;
-      slot_fill = slot_fill == 2 ? 0 : slot_fill + 1;
-    }
-  }
-
-  if (stamp) p.stamps[22] = __builtin_amdgcn_s_memtime();
-  // epilogue: transposed through LDS so every lane moves float4s (see conv3x3_fwd_kernel); scales divided out here
-  const float* __restrict__ res = p.res;
-  const float* __restrict__ cbp = p.cbias;
-  float* __restrict__ yout = p.y;
-  constexpr int TS = 64 + 4;
-  float* stage = reinterpret_cast<float*>(smem) + wave * 32 * TS;
-  const int c4 = lane & 15, prl = lane >> 4;
-  const int nb = n0 + wn * 64 + c4 * 4;
-  f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
-  if (p.bias) bias4 = *reinterpret_cast<const f32x4*>(p.bias + nb);
-  if (p.cbias_mode == 1) {
-    const f32x4 c = *reinterpret_cast<const f32x4*>(cbp + (size_t)b * N + nb);
-    bias4[0] += c[0]; bias4[1] += c[1]; bias4[2] += c[2]; bias4[3] += c[3];
-  }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    __syncthreads();
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) stage[mfma32_row(r, lane) * TS + nt * 32 + li] = (acc[mt][nt][r] * inv_x) * inv_w;
-    __syncthreads();
-    const int hh = h0 + wm * MT + mt;
-    const size_t rowbase = (((size_t)b * p.H + hh) * kW) * N + nb;
-    f32x4 add[8];
-#pragma unroll
-    for (int it = 0; it < 8; ++it) add[it] = bias4;
-    if (p.cbias_mode == 2) {
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const f32x4 c = *reinterpret_cast<const f32x4*>(cbp + rowbase + (size_t)(it * 4 + prl) * N);
-        add[it][0] += c[0]; add[it][1] += c[1]; add[it][2] += c[2]; add[it][3] += c[3];
-      }
-    }
-    if (res) {
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const f32x4 c = *reinterpret_cast<const f32x4*>(res + rowbase + (size_t)(it * 4 + prl) * N);
-        add[it][0] += c[0]; add[it][1] += c[1]; add[it][2] += c[2]; add[it][3] += c[3];
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(stage + (it * 4 + prl) * TS + c4 * 4);
-      const f32x4 o = {a[0] + add[it][0], a[1] + add[it][1], a[2] + add[it][2], a[3] + add[it][3]};
-      *reinterpret_cast<f32x4*>(yout + rowbase + (size_t)(it * 4 + prl) * N) = o;
-    }
-  }
-  if (stamp) { p.stamps[23] = __builtin_amdgcn_s_memtime(); p.stamps[31] = __builtin_amdgcn_s_memrealtime(); }
-}
-
-// ---- "big tile" variant: block = 8 image rows x 128 couts, wave = 4 rows x 64 couts (4 x 2 MFMA tiles, 128
+// ---- the 8-row 32x32x16 kernel: block = 8 image rows x 128 couts, wave = 4 rows x 64 couts (4 x 2 MFMA tiles, 128
 // accumulator registers, one wave per SIMD).  The weight fragments are read straight from the packed global tensor
 // (L2/L1 resident, two stages ahead, no LDS copy and no per-stage barrier); only the activation patch goes through
-// LDS, double buffered, with one barrier per 16-channel chunk.  LDS traffic per MFMA is half that of the 2 x 2
-// variant above, which is LDS-bandwidth bound with three passes per product.
+// LDS, double buffered, with one barrier per 16-channel chunk.  With three passes per product a block of 4 rows and
+// 2 x 2 MFMA tiles that also staged its weights in LDS was LDS-bandwidth bound; this tiling halves the LDS traffic
+// per MFMA.
 constexpr int TR2 = 8;
 constexpr int PATCH2_B = (TR2 + 2) * kPW * PIXB;     // 27200
 constexpr int SMEM2_B = 2 * PATCH2_B + 64;           // 54464 (+ dummy store target)
@@ -592,8 +370,11 @@ __global__ void conv3x3_pack_f16x3_kernel(const float* __restrict__ w, _Float16*
 
 
 // ------------------------------------------------------------------------------------------------ wgrad
-// dW[t][ci][co] = sum_pixels x[p + shift_t][ci] * dy[p][co] with the same 3-pass split; operands fetched with the
-// transposing LDS read ds_read_b64_tr_b16 exactly as in conv3x3_wgrad_bf16x6_kernel (two planes instead of three).
+// dW[t][ci][co] = sum_pixels x[p + shift_t][ci] * dy[p][co] with the same 3-pass split.  The contraction index is
+// the pixel, while both tensors are stored channel-contiguous, so the operands are fetched with the transposing LDS
+// read ds_read_b64_tr_b16 (a 4 k x 16 channel block per 16-lane group, delivered k-major): a tap shift is then a
+// whole-row address offset and every read stays 8-byte aligned.  LDS rows are 64 B (32 channels of one split plane),
+// which makes the two 16-lane groups of a half-wave cover all 64 banks exactly once.
 constexpr int WG_T = 64, WG_ROWS = 2;
 constexpr int XPIX = (WG_ROWS + 2) * kPW;                 // 136 halo-patch pixels
 constexpr int X_HALF = XPIX * 64, X_PLANE = 2 * X_HALF;   // bytes
@@ -946,7 +727,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
     *reinterpret_cast<i32x4*>(buf + dst) = dreg[i];
   };
 
-  // lane part of every transposing read (see conv3x3_wgrad_bf16x6_kernel)
+  // lane part of every transposing read: row q of the 4-k block, columns 4p..4p+3 of this group's 16 channels,
+  // k half = lh  (MFMA operand element j <-> k = 8 lh + j)
   const int grp_q = (lane & 15) >> 2, grp_p = lane & 3, cb16 = ((lane >> 4) & 1) * 16;
   const int lane_off = (8 * lh + grp_q) * 64 + (cb16 + 4 * grp_p) * 2;
   const int xa_off = (wci * 2) * X3_HALF + lane_off;
@@ -1511,7 +1293,7 @@ MULAN_API int mulan_conv3x3_pack_f16x3(const float* w, void* wp, const unsigned*
   MULAN_CHECK_LAUNCH();
 }
 
-// Eligibility: W == 32, H % 4 == 0, C % 16 == 0, N % 128 == 0 (the ResBlock convolutions); everything else goes
+// Eligibility: W == 32, H % 8 == 0, C % 16 == 0, N % 128 == 0 (the ResBlock convolutions); everything else goes
 // through mulan_conv3x3_fwd.  xmax = mulan_absmax_rows(x, B rows); wp / wmax from mulan_conv3x3_pack_f16x3.
 MULAN_API size_t mulan_conv3x3_planes_bytes(int B, int H, int W, int C) { return (size_t)B * H * W * C * 4; }
 
@@ -1524,37 +1306,25 @@ static int conv3x3_fwd_f16x3_impl(const float* x, const unsigned* xmax, const vo
                                   const float* bias, const float* cbias, int cbias_mode, const float* res, float* y,
                                   void* xs, unsigned* ymax, int alone, int B, int H, int W, int C, int N,
                                   hipStream_t stream) {
-  if (W != kW || H % TROWS != 0 || B <= 0 || C % CK != 0 || C <= 0 || N % BN != 0 || N <= 0 || !xmax || !wmax)
+  if (W != kW || H % TR2 != 0 || B <= 0 || C % CK != 0 || C <= 0 || N % BN != 0 || N <= 0 || !xmax || !wmax)
     return (int)hipErrorInvalidValue;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_f16x3_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_B);
-    if (e != hipSuccess) return (int)e;
-    configured = true;
-  }
   ConvArgsH a{x, xmax, static_cast<const unsigned char*>(wp), wmax, bias, cbias, res, y, B, H, C, N,
               cbias ? cbias_mode : 0, g_mulan_debug_buffer, static_cast<unsigned char*>(xs), ymax};
   a.alone = alone;
-  if (xs && (H % TR2 != 0 || (size_t)B * H * W * C * 4 >= 0x80000000ull)) return (int)hipErrorInvalidValue;
-  if (ymax && (H % TR2 != 0 || (H / TR2) * (N / BN) > kMaxParts)) return (int)hipErrorInvalidValue;
-  // default: the 16x16x32 / two-blocks-per-CU kernel (conv3x3_f16x3_v3.hip); tune[3] = 2 / 1: dev A/B switches to the
-  // 32x32x16 one-block-per-CU kernel / the 2 x 2-tile kernel below
+  if (xs && (size_t)B * H * W * C * 4 >= 0x80000000ull) return (int)hipErrorInvalidValue;
+  if (ymax && (H / TR2) * (N / BN) > kMaxParts) return (int)hipErrorInvalidValue;
+  // default: the 16x16x32 / two-blocks-per-CU kernel (conv3x3_f16x3_v3.hip); otherwise (C % 32 != 0, a tensor of 2 GiB,
+  // or tune[3] = 2, the dev A/B switch -- any non-zero value acts alike) the 32x32x16 one-block-per-CU kernel above
   if (g_mulan_tune[3] == 0 && mulan_conv3x3_f16x3_v3_eligible(H, C, N) && (size_t)B * H * W * C * 4 < 0x80000000ull)
     return mulan_launch_conv3x3_f16x3_v3(a, stream);
-  if (H % TR2 == 0 && (g_mulan_tune[3] != 1 || xs || ymax)) {   // tune[3] = 1: dev A/B switch to the 2 x 2-tile variant
-    static bool configured2 = false;
-    if (!configured2) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_f16x3_v2_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2_B);
-      if (e != hipSuccess) return (int)e;
-      configured2 = true;
-    }
-    hipLaunchKernelGGL(conv3x3_f16x3_v2_kernel, dim3(B * (H / TR2), N / BN), dim3(256), SMEM2_B, stream, a);
-    MULAN_CHECK_LAUNCH();
+  static bool configured2 = false;
+  if (!configured2) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_f16x3_v2_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2_B);
+    if (e != hipSuccess) return (int)e;
+    configured2 = true;
   }
-  dim3 grid(B * (H / TROWS), N / BN);
-  hipLaunchKernelGGL(conv3x3_f16x3_kernel, grid, dim3(256), SMEM_B, stream, a);
+  hipLaunchKernelGGL(conv3x3_f16x3_v2_kernel, dim3(B * (H / TR2), N / BN), dim3(256), SMEM2_B, stream, a);
   MULAN_CHECK_LAUNCH();
 }
 

@@ -8,13 +8,9 @@ namespace f16x3 {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kW = 32, kPW = 34, CK = 16, TROWS = 4;
+constexpr int kW = 32, kPW = 34, CK = 16;
 constexpr int PIXB = 80;                        // bytes per patch pixel: 2 planes x 32 B + 16 pad ((PIXB/16) odd)
-constexpr int NB = 80;                          // bytes per cout row of a weight tile
-constexpr int PATCH_B = (TROWS + 2) * kPW * PIXB;   // 16320
 constexpr int BN = 128;
-constexpr int WT_B = BN * NB;                   // 10240
-constexpr int SMEM_B = PATCH_B + 3 * WT_B;      // 47040 (dynamic shared memory): 1 patch + 3-deep weight ring
 
 // ---- power-of-two scales from an absolute maximum given as fp32 bits
 // s = 2^(140 - e) with e the (clamped) biased exponent of the maximum: max * s in [2^13, 2^14).  inv = 1 / s.

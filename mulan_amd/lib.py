@@ -22,11 +22,6 @@ SIGNATURES = {
     "mulan_conv3x3_wflip": [P, P, I, I, P],
     "mulan_conv3x3_wgrad_workspace": [I, I, I, I, I],
     "mulan_conv3x3_wgrad": [P, P, P, P, I, I, I, I, I, I, P],
-    "mulan_conv3x3_pack_bf16x6_bytes": [I, I],
-    "mulan_conv3x3_pack_bf16x6": [P, P, I, I, I, P],
-    "mulan_conv3x3_fwd_bf16x6": [P, P, P, P, I, P, P, I, I, I, I, I, P],
-    "mulan_conv3x3_wgrad_bf16x6_workspace": [I, I, I, I, I],
-    "mulan_conv3x3_wgrad_bf16x6": [P, P, P, P, I, I, I, I, I, I, P],
     "mulan_absmax_rows": [P, P, I, Z, P],
     "mulan_add_absmax_rows": [P, P, P, P, I, Z, P],
     "mulan_add_absmax_rows_colsum": [P, P, P, P, P, I, Z, I, P],
@@ -143,8 +138,7 @@ SIGNATURES = {
     "mulan_stream_wait_signal": [P, P, ctypes.c_uint],
     "mulan_signal_read": [P, P],
 }
-_RESTYPES = {"mulan_rk_workspace_bytes": c_size_t, "mulan_global_norm_clip_workspace": c_size_t, "mulan_conv3x3_wgrad_workspace": c_size_t, "mulan_conv3x3_pack_bf16x6_bytes": c_size_t, "mulan_conv3x3_wgrad_bf16x6_workspace": c_size_t,
-             "mulan_conv3x3_pack_f16x3_bytes": c_size_t, "mulan_conv3x3_planes_bytes": c_size_t, "mulan_linear_pack_f16x3_bytes": c_size_t,
+_RESTYPES = {"mulan_rk_workspace_bytes": c_size_t, "mulan_global_norm_clip_workspace": c_size_t, "mulan_conv3x3_wgrad_workspace": c_size_t, "mulan_conv3x3_pack_f16x3_bytes": c_size_t, "mulan_conv3x3_planes_bytes": c_size_t, "mulan_linear_pack_f16x3_bytes": c_size_t,
              "mulan_linear_wgrad_f16x3_planes_workspace": c_size_t, "mulan_linear_wgrad_f16x3_x32_workspace": c_size_t,
              "mulan_conv3x3_wgrad_f16x3_planes_workspace": c_size_t, "mulan_conv3x3_wgrad_f16x3_workspace": c_size_t, "mulan_gemm_workspace": c_size_t, "mulan_version": c_char_p}
 

@@ -20,10 +20,13 @@ HW = H * W
 D = HW * 3
 KERNEL_TIMER = None   # bench.py sets this to a list to time the dominant kernel with HIP events
 # "f32": exact-fp32 MFMA (v_mfma_f32_32x32x2_f32).  "f16x3": 3-pass fp16 split (two scaled fp16 pieces per fp32 operand)
-# with fp32-equivalent products.  "bf16x6": 6-pass bf16 split with fp32-equivalent products
-# (XLA's float32/HIGHEST matmul precision) for the eligible convolutions.  MULAN_CONV_MODE overrides.
+# with fp32-equivalent products, for the eligible convolutions and dense layers.  MULAN_CONV_MODE overrides; any other
+# value would otherwise fall through every `CONV_MODE == "f16x3"` test into the fp32 kernels, so it is refused here.
 import os as _os
+CONV_MODES = ("f16x3", "f32")
 CONV_MODE = _os.environ.get("MULAN_CONV_MODE", "f16x3")
+if CONV_MODE not in CONV_MODES:
+    raise ValueError(f"MULAN_CONV_MODE must be one of {', '.join(CONV_MODES)}; got {CONV_MODE!r}")
 
 
 def _c(t):
@@ -409,20 +412,16 @@ def _prepacked(w, direction):
 
 
 def _pack_weights(w, C, N, flip, wmax=None):
-    """weights pre-split into the LDS tile layout of the fast convolution kernels; returns (wp, wmax or None)"""
+    """weights pre-split into the LDS tile layout of the f16x3 convolution kernels; returns (wp, wmax)"""
     L = lib.load()
     pre = _prepacked(w, int(flip))
     if pre is not None:
         return pre
-    if CONV_MODE == "f16x3":
-        wp = torch.empty(L.mulan_conv3x3_pack_f16x3_bytes(C, N), device=w.device, dtype=torch.uint8)
-        if wmax is None:
-            wmax = absmax_rows(w.view(1, -1))
-        call("mulan_conv3x3_pack_f16x3", ptr(w), ptr(wp), ptr(wmax), C, N, flip, stream())
-        return wp, wmax
-    wp = torch.empty(L.mulan_conv3x3_pack_bf16x6_bytes(C, N), device=w.device, dtype=torch.uint8)
-    call("mulan_conv3x3_pack_bf16x6", ptr(w), ptr(wp), C, N, flip, stream())
-    return wp, None
+    wp = torch.empty(L.mulan_conv3x3_pack_f16x3_bytes(C, N), device=w.device, dtype=torch.uint8)
+    if wmax is None:
+        wmax = absmax_rows(w.view(1, -1))
+    call("mulan_conv3x3_pack_f16x3", ptr(w), ptr(wp), ptr(wmax), C, N, flip, stream())
+    return wp, wmax
 
 
 def planes_eligible(C, N):
@@ -440,7 +439,7 @@ def conv3x3_raw(x, w, bias=None, cbias=None, res=None, xmax=None, planes=False, 
     mode = 0
     if cbias is not None:
         mode = 1 if cbias.dim() == 2 else 2
-    fast = CONV_MODE in ("bf16x6", "f16x3") and C % 16 == 0 and N % 128 == 0
+    fast = CONV_MODE == "f16x3" and C % 16 == 0 and N % 128 == 0
     flops = 2.0 * B * HW * 9 * C * N
     if not fast:
         variant = "<128,2,2>" if N > 64 else ("<64,2,2>" if N > 32 else "<32,4,1>")
@@ -450,24 +449,17 @@ def conv3x3_raw(x, w, bias=None, cbias=None, res=None, xmax=None, planes=False, 
         return y
     assert fast or not planes
     wp, wmax = _pack_weights(w, C, N, 0, wmax)
-    if CONV_MODE == "f16x3":
-        if xmax is None:
-            xmax = absmax_rows(x)
-        xs = torch.empty(B * HW * C * 4, device=x.device, dtype=torch.uint8) if planes else None
-        # by-product: the maxima of y, left on the tensor for whichever f16x3 kernel reads it next
-        ymax = torch.empty((B, MAX_PARTS), device=x.device, dtype=torch.int32) if (H // 8) * (N // 128) <= MAX_PARTS else None
-        _timed("conv3x3_f16x3_kernel", flops,
-               lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(x), ptr(xmax), ptr(wp), ptr(wmax), ptr(bias), ptr(cbias), mode,
-                            ptr(res), ptr(y), ptr(xs), ptr(ymax), _alone(), B, H, W, C, N, stream()))
-        if ymax is not None:
-            _leave(y, "_absmax", ymax)
-        if planes:
-            return y, xs
-    else:
-        _timed("conv3x3_bf16x6_kernel", flops,
-               lambda: call("mulan_conv3x3_fwd_bf16x6", ptr(x), ptr(wp), ptr(bias), ptr(cbias), mode, ptr(res), ptr(y),
-                            B, H, W, C, N, stream()))
-    return y
+    if xmax is None:
+        xmax = absmax_rows(x)
+    xs = torch.empty(B * HW * C * 4, device=x.device, dtype=torch.uint8) if planes else None
+    # by-product: the maxima of y, left on the tensor for whichever f16x3 kernel reads it next
+    ymax = torch.empty((B, MAX_PARTS), device=x.device, dtype=torch.int32) if (H // 8) * (N // 128) <= MAX_PARTS else None
+    _timed("conv3x3_f16x3_kernel", flops,
+           lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(x), ptr(xmax), ptr(wp), ptr(wmax), ptr(bias), ptr(cbias), mode,
+                        ptr(res), ptr(y), ptr(xs), ptr(ymax), _alone(), B, H, W, C, N, stream()))
+    if ymax is not None:
+        _leave(y, "_absmax", ymax)
+    return (y, xs) if planes else y
 
 
 def conv3x3_dgrad_raw(dy, w, dymax=None, planes=False, wmax=None, want_max=False):
@@ -475,29 +467,22 @@ def conv3x3_dgrad_raw(dy, w, dymax=None, planes=False, wmax=None, want_max=False
     want_max (f16x3 mode): the kernel leaves the maxima of dx on the tensor (a GroupNorm backward that hands its own
     result on as planes needs them for its bound)."""
     C, N = w.shape[2], w.shape[3]
-    if CONV_MODE in ("bf16x6", "f16x3") and N % 16 == 0 and C % 128 == 0:
+    if CONV_MODE == "f16x3" and N % 16 == 0 and C % 128 == 0:
         B = dy.shape[0]
         dx = torch.empty((B, HW, C), device=dy.device, dtype=torch.float32)
         wp, wmax = _pack_weights(w, C, N, 1, wmax)
         flops = 2.0 * B * HW * 9 * C * N
-        if CONV_MODE == "f16x3":
-            if dymax is None:
-                dymax = absmax_rows(dy)
-            dys = torch.empty(B * HW * N * 4, device=dy.device, dtype=torch.uint8) if planes else None
-            dxmax = (torch.empty((B, MAX_PARTS), device=dy.device, dtype=torch.int32)
-                     if want_max and (H // 8) * (C // 128) <= MAX_PARTS else None)
-            _timed("conv3x3_f16x3_kernel", flops,
-                   lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(dy), ptr(dymax), ptr(wp), ptr(wmax), None, None, 0, None,
-                                ptr(dx), ptr(dys), ptr(dxmax), _alone(), B, H, W, N, C, stream()))
-            if dxmax is not None:
-                _leave(dx, "_absmax", dxmax)
-            if planes:
-                return dx, dys
-        else:
-            _timed("conv3x3_bf16x6_kernel", flops,
-                   lambda: call("mulan_conv3x3_fwd_bf16x6", ptr(dy), ptr(wp), None, None, 0, None, ptr(dx), B, H, W, N, C,
-                                stream()))
-        return dx
+        if dymax is None:
+            dymax = absmax_rows(dy)
+        dys = torch.empty(B * HW * N * 4, device=dy.device, dtype=torch.uint8) if planes else None
+        dxmax = (torch.empty((B, MAX_PARTS), device=dy.device, dtype=torch.int32)
+                 if want_max and (H // 8) * (C // 128) <= MAX_PARTS else None)
+        _timed("conv3x3_f16x3_kernel", flops,
+               lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(dy), ptr(dymax), ptr(wp), ptr(wmax), None, None, 0, None,
+                            ptr(dx), ptr(dys), ptr(dxmax), _alone(), B, H, W, N, C, stream()))
+        if dxmax is not None:
+            _leave(dx, "_absmax", dxmax)
+        return (dx, dys) if planes else dx
     wT = torch.empty((3, 3, N, C), device=w.device, dtype=torch.float32)
     call("mulan_conv3x3_wflip", ptr(w), ptr(wT), C, N, stream())
     return conv3x3_raw(dy, wT)
@@ -555,15 +540,14 @@ def _fresh(view):
 
 def conv3x3_wgrad_raw(x, dy, out=None, xmax=None, dymax=None):
     B, C, N = x.shape[0], x.shape[-1], dy.shape[-1]
-    fast = CONV_MODE in ("bf16x6", "f16x3") and C % 4 == 0 and N % 4 == 0
-    kind = CONV_MODE if fast else ""
-    fn = "mulan_conv3x3_wgrad" + ("_" + kind if fast else "")
+    fast = CONV_MODE == "f16x3" and C % 4 == 0 and N % 4 == 0
+    fn = "mulan_conv3x3_wgrad" + ("_f16x3" if fast else "")
     nbytes = getattr(lib.load(), fn + "_workspace")(B, H, W, C, N)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
     dw = out if out is not None else torch.empty((3, 3, C, N), device=x.device, dtype=torch.float32)
-    name = "conv3x3_wgrad" + ("_" + kind if fast else "") + "_kernel+slab_reduce"
+    name = "conv3x3_wgrad" + ("_f16x3" if fast else "") + "_kernel+slab_reduce"
     flops = 2.0 * B * HW * 9 * C * N
-    if kind == "f16x3":
+    if fast:
         xmax = absmax_rows(x) if xmax is None else xmax
         dymax = absmax_rows(dy) if dymax is None else dymax
         _timed(name, flops, lambda: call(fn, ptr(x), ptr(xmax), ptr(dy), ptr(dymax), ptr(dw), ptr(ws), B, H, W, C, N, 0,

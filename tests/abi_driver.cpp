@@ -279,6 +279,8 @@ void error_convention(hipStream_t stream) {
          "W != 32 is refused");
   expect(mulan_conv3x3_fwd_f16x3(a.p, nullptr, wp.p, m.p, nullptr, nullptr, 0, nullptr, b.p, nullptr, nullptr, 1, 32, 32, 32, 128, stream) != 0,
          "missing maxima are refused");
+  expect(mulan_conv3x3_fwd_f16x3(a.p, m.p, wp.p, m.p, nullptr, nullptr, 0, nullptr, b.p, nullptr, nullptr, 1, 12, 32, 32, 128, stream) != 0,
+         "H % 8 != 0 is refused");
   expect(mulan_conv3x3_wgrad_f16x3(a.p, m.p, b.p, m.p, a.p, b.p, 0, 32, 32, 32, 128, 0, stream) != 0, "B == 0 is refused");
   expect(hipStreamSynchronize(stream) == hipSuccess && hipGetLastError() == hipSuccess, "no sticky device error after refused calls");
   void* sig = nullptr;

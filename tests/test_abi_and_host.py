@@ -792,3 +792,19 @@ def test_step_form_choice_only_explicit_requests_make_a_failed_capture_fatal():
     assert f(True, "0", 1, 128, 128, False) == (False, True)         # asked for by config, switched off by the environment
     # the opt-in overlap forms keep the replay as their default
     assert f(None, "", 8, 1024, 128, True) == (True, False)
+
+
+def test_unknown_conv_mode_is_refused_at_import():
+    """MULAN_CONV_MODE takes f16x3 and f32.  Any other value (the retired bf16x6 among them) would pass every
+    `CONV_MODE == "f16x3"` test as false and run the fp32 kernels without a word, so importing mulan_amd.ops with it
+    fails and names both valid modes; a valid value imports.  Fresh interpreters: this one has ops imported already."""
+    import subprocess
+    import sys
+    def child(mode):
+        return subprocess.run([sys.executable, "-c", "import mulan_amd.ops"], capture_output=True, text=True, timeout=300,
+                              cwd=ROOT, env=dict(os.environ, MULAN_CONV_MODE=mode))
+    bad = child("bf16x6")
+    assert bad.returncode != 0, (bad.stdout[-2000:], bad.stderr[-2000:])
+    assert "ValueError" in bad.stderr and "f16x3" in bad.stderr and "f32" in bad.stderr and "'bf16x6'" in bad.stderr, bad.stderr[-2000:]
+    good = child("f32")
+    assert good.returncode == 0, (good.stdout[-2000:], good.stderr[-3000:])

@@ -15,8 +15,8 @@ from oracle import torch_ref as tr
 
 @pytest.fixture(scope="module")
 def ops():
-    """This module pins the exact-fp32 MFMA convolution kernels; tests/test_gpu_bf16x6.py covers the default
-    6-pass bf16 split kernels against the same oracle."""
+    """This module pins the exact-fp32 MFMA convolution kernels; tests/test_gpu_f16x3.py covers the default
+    3-pass fp16 split kernels against the same oracle."""
     from mulan_amd import ops as _ops
     _ops.lib.load()
     saved = _ops.CONV_MODE
@@ -625,3 +625,10 @@ def test_oracle_is_the_same_on_host_and_device(monkeypatch):
     for k in gc:      # (1e-13 of the largest gradient: the key bias of the attention block has a gradient that is zero
         #                 identically -- softmax ignores a constant added to a row of scores -- and holds rounding noise)
         assert float((gc[k] - gd[k]).abs().max()) <= 1e-9 * float(gc[k].abs().max()) + 1e-13 * gmax, k
+
+
+def test_f32_mfma_whole_model_parity(ops, monkeypatch):
+    """a MuLAN train-mode step with MULAN_CONV_MODE=f32 (exact-fp32 MFMA kernels): the parity bars of run_case"""
+    from tests.test_gpu_model import run_case
+    monkeypatch.setattr(ops, "CONV_MODE", "f32")
+    run_case("mulan_epsilon", "vdm", False, train=True)

@@ -668,8 +668,8 @@ def test_grouped_film_projections_match_per_block_gemms():
 
 
 def test_arithmetic_modes_agree_over_training_steps():
-    """Five optimiser steps from the same initialisation, data and noise in the three convolution modes (f16x3 with
-    the plane hand-over, grouped FiLM projections and once-per-step weight preparation; bf16x6; exact-fp32 MFMA):
+    """Five optimiser steps from the same initialisation, data and noise in the two convolution modes (f16x3 with
+    the plane hand-over, grouped FiLM projections and once-per-step weight preparation; exact-fp32 MFMA):
     the BPD trajectories agree to fp32 noise, i.e. far inside the +-0.005 BPD bar."""
     import os
     from mulan_amd import ops
@@ -679,7 +679,7 @@ def test_arithmetic_modes_agree_over_training_steps():
     saved = ops.CONV_MODE
     traj = {}
     try:
-        for mode in ("f32", "bf16x6", "f16x3"):
+        for mode in ("f32", "f16x3"):
             ops.CONV_MODE = mode
             config = load_config_file(os.path.join(root, "ldm", "configs", "cifar10-conditioned.py"))
             config.data.dataset = 'synthetic'
@@ -700,7 +700,7 @@ def test_arithmetic_modes_agree_over_training_steps():
         ops.CONV_MODE = saved
     assert np.all(np.isfinite(traj["f32"]))
     print("BPD trajectories:", {k: [round(float(x), 5) for x in v] for k, v in traj.items()})
-    for mode in ("bf16x6", "f16x3"):
+    for mode in ("f16x3",):
         assert np.abs(traj[mode] - traj["f32"]).max() < 5e-4, (mode, traj[mode], traj["f32"])   # measured: 1e-5
 
 
