@@ -37,19 +37,9 @@ struct GnArgs {
   int xstats_tiles;                           // row tiles per image in xstats1 / xstats2 (the producer's tile height: 4, 8 or 16)
 };
 
-__device__ __forceinline__ void drop4(f32x4& v, float keep, unsigned long long seed, unsigned long long ctr) {
-  // keep-mask = (u32 < floor(keep * 2^32)); jax.random.bernoulli(keep) semantics, scaled by 1/keep
-  // (flax nn.Dropout).  Integer compare so the numpy oracle reproduces the mask bit for bit.
-  const Philox4 r = philox4x32_10(seed, ctr, 0ull);
-  const uint32_t thr = (uint32_t)((double)keep * 4294967296.0);
-  const float inv = 1.f / keep;
-  v[0] = (r.x < thr) ? v[0] * inv : 0.f;
-  v[1] = (r.y < thr) ? v[1] * inv : 0.f;
-  v[2] = (r.z < thr) ? v[2] * inv : 0.f;
-  v[3] = (r.w < thr) ? v[3] * inv : 0.f;
-}
-
-// 4 keep-bits (bit e = element e kept) of one float4: same Philox draw and integer compare as drop4
+// 4 keep-bits (bit e = element e kept) of one float4: keep-mask = (u32 < thr), thr = floor(keep * 2^32) --
+// jax.random.bernoulli(keep) semantics; the kept elements are scaled by 1/keep (flax nn.Dropout).  Integer compare so
+// the numpy oracle reproduces the mask bit for bit.
 __device__ __forceinline__ unsigned drop_bits4(uint32_t thr, unsigned long long seed, unsigned long long ctr) {
   const Philox4 r = philox4x32_10(seed, ctr, 0ull);
   return (r.x < thr ? 1u : 0u) | (r.y < thr ? 2u : 0u) | (r.z < thr ? 4u : 0u) | (r.w < thr ? 8u : 0u);
@@ -59,23 +49,15 @@ __device__ __forceinline__ float apply_bit(float v, float inv, unsigned bits, in
   const int m = (int)(bits << (31 - pos)) >> 31;                 // all ones / zero
   return __uint_as_float(__float_as_uint(v * inv) & (unsigned)m);
 }
-// sigmoid / SiLU / SiLU' on the hardware exp2 and reciprocal (1 ulp each): the accurate expf + IEEE division cost
-// ~25 VALU slots per element, which made these HBM-shaped kernels VALU-bound (19 us of memory time + 26 us of
-// arithmetic per launch, measured); relative error ~3e-7
-__device__ __forceinline__ float sigmoid_fast(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
-__device__ __forceinline__ float silu_fast(float x) { return x * sigmoid_fast(x); }
-__device__ __forceinline__ float silu_grad_fast(float x) {
-  const float sg = sigmoid_fast(x);
-  return sg * (1.f + x * (1.f - sg));
-}
 
 // two-wide arithmetic: clang lowers <2 x float> mul / add / fma to v_pk_*_f32 (one issue slot for two elements)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 lo2(const f32x4& v) { return f32x2{v[0], v[1]}; }
 __device__ __forceinline__ f32x2 hi2(const f32x4& v) { return f32x2{v[2], v[3]}; }
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// sigmoid (SiLU and SiLU' are formed from it) on the hardware exp2 and reciprocal (1 ulp each): the accurate expf + IEEE
+// division cost ~25 VALU slots per element, which made these HBM-shaped kernels VALU-bound (19 us of memory time + 26 us
+// of arithmetic per launch, measured); relative error ~3e-7
 __device__ __forceinline__ f32x2 sigmoid_fast2(f32x2 x) {
   const f32x2 t = x * -1.4426950408889634f;
   const f32x2 d = f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + 1.f;
@@ -240,7 +222,7 @@ struct GnBwdArgs {
   float* dgamma_part; float* dbeta_part;       // [B,C1+C2] per-sample partials
   int B, G; int act; float keep; unsigned long long seed, offset;
   int accumulate;                              // dx += instead of dx =
-  unsigned* dx1max; unsigned* dx2max;          // optional [B][16]: partial maxima of |dx1|, |dx2| (single-pass kernel)
+  unsigned* dx1max; unsigned* dx2max;          // optional [B][16]: partial maxima of |dx1|, |dx2|
   const float* add1; const float* add2;        // optional: dx1 += add1, dx2 += add2 (gradient of a skip path of x)
   float* dxsum_part;                           // optional [B, C1+C2]: per-sample channel sums of the written dx
   const unsigned long long* seed_dev;          // optional: dropout seed = seed ^ seed_dev[0] (as in the forward pass)
@@ -250,111 +232,20 @@ struct GnBwdArgs {
   float* dgamma; float* dbeta;                 // [Ct] totals
   float* dxsum; float* dxsum2;                 // optional [C1] each: sum over samples of dxsum_part's x1 columns (the bias
                                                // gradient of the convolution in front, and of a shortcut layer sharing it)
-  // optional (single-pass kernel, C2 == 0, no add1, no accumulate): dx1 is written as the split fp16 operand planes of
+  // optional (C2 == 0, no add1, no accumulate): dx1 is written as the split fp16 operand planes of
   // the input-gradient convolution / weight-gradient kernel in front ([B][C1/16][HW][plane][16]) INSTEAD of as fp32,
   // scaled by an a-priori bound (below) that dx1max receives; dymax: [B][16] maxima of dy (the bound needs max|dy[b]|)
   unsigned char* dx1planes; const unsigned* dymax;
-  // optional (single-pass kernel): the keep-bits the forward kernel stored (GnArgs::maskbits) instead of re-drawing them
-  // (10 Philox rounds per float4: ~45 % of this kernel's arithmetic in the dropout layers)
+  // optional: the keep-bits the forward kernel stored (GnArgs::maskbits) instead of re-drawing them
+  // (10 Philox rounds per float4: ~45 % of the backward kernel's arithmetic in the dropout layers)
   const unsigned* maskbits;
-  // optional (single-pass kernel): a second gradient that reaches x1 from outside -- dx1 = (dx1 + add1) + add1b: the
+  // optional: a second gradient that reaches x1 from outside -- dx1 = (dx1 + add1) + add1b: the
   // gradient a block output receives through its U-Net skip connection, added here instead of by a kernel of its own
   const float* add1b;
   // streaming kernel only: the partial sums of g gamma and g gamma xhat (g = dy mask / keep act'(u)) per image, 8-row
   // tile and channel quad, [B][HW / 256][(C1 + C2) / 4][2], as the input-gradient convolution that produced dy left them
   const float* gstats;
 };
-
-__global__ __launch_bounds__(256) void gn_bwd_kernel(GnBwdArgs p) {
-  if (p.seed_dev) p.seed ^= p.seed_dev[0];
-  __shared__ float red[64];
-  __shared__ float cred[2 * 4 * 32];
-  const int tid = threadIdx.x, quad = tid & 7, prow = tid >> 3;
-  const int b = blockIdx.x, Ct = p.C1 + p.C2;
-  const int c0 = blockIdx.y * 32;
-  const int cpg = Ct / p.G, qpg = cpg >> 2;
-  const float* src; float* dxp; int ld, cs;
-  if (c0 < p.C1) { src = p.x1; dxp = p.dx1; ld = p.C1; cs = c0; }
-  else { src = p.x2; dxp = p.dx2; ld = p.C2; cs = c0 - p.C1; }
-  src += (size_t)b * HW * ld + cs + quad * 4;
-  dxp += (size_t)b * HW * ld + cs + quad * 4;
-  const int c = c0 + quad * 4, g = c / cpg;
-  const float mean = p.mean[b * p.G + g], rstd = p.rstd[b * p.G + g];
-  const f32x4 ga = *reinterpret_cast<const f32x4*>(p.gamma + c);
-  const f32x4 be = *reinterpret_cast<const f32x4*>(p.beta + c);
-  const float* dyp = p.dy + (size_t)b * HW * Ct + c;
-
-  // pass 1: accumulate group sums and per-channel partials (x, dy are re-read in pass 2: L2/MALL)
-  float s1 = 0.f, s2 = 0.f;
-  f32x4 dg = {0.f, 0.f, 0.f, 0.f}, db = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    const int px = prow + 32 * i;
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(src + (size_t)px * ld);
-    f32x4 d = *reinterpret_cast<const f32x4*>(dyp + (size_t)px * Ct);
-    if (p.keep < 1.f) {
-      const unsigned long long idx4 = (((unsigned long long)b * HW + px) * Ct + c) >> 2;
-      drop4(d, p.keep, p.seed, p.offset + idx4);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float xhat = (xv[e] - mean) * rstd;
-      const float u = xhat * ga[e] + be[e];
-      const float gu = p.act ? d[e] * silu_grad_f(u) : d[e];
-      dg[e] += gu * xhat;
-      db[e] += gu;
-      const float dxh = gu * ga[e];
-      s1 += dxh;
-      s2 += dxh * xhat;
-    }
-  }
-  group_reduce2(s1, s2, quad, qpg, red);
-  // per-channel partial sums over the 32 prow lanes
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-#pragma unroll
-    for (int o = 8; o < 64; o <<= 1) { dg[e] += __shfl_xor(dg[e], o, 64); db[e] += __shfl_xor(db[e], o, 64); }
-  }
-  const int wave = tid >> 6, lane = tid & 63;
-  if (lane < 8) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { cred[wave * 32 + lane * 4 + e] = dg[e]; cred[128 + wave * 32 + lane * 4 + e] = db[e]; }
-  }
-  __syncthreads();
-  if (tid < 32) {
-    const float a = cred[tid] + cred[32 + tid] + cred[64 + tid] + cred[96 + tid];
-    const float bb = cred[128 + tid] + cred[160 + tid] + cred[192 + tid] + cred[224 + tid];
-    p.dgamma_part[(size_t)b * Ct + c0 + tid] = a;
-    p.dbeta_part[(size_t)b * Ct + c0 + tid] = bb;
-  }
-  const float inv_n = 1.f / (float)(HW * cpg);
-  const float m1 = s1 * inv_n, m2 = s2 * inv_n;
-  // pass 2: dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat))
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    const int px = prow + 32 * i;
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(src + (size_t)px * ld);
-    f32x4 d = *reinterpret_cast<const f32x4*>(dyp + (size_t)px * Ct);
-    if (p.keep < 1.f) {
-      const unsigned long long idx4 = (((unsigned long long)b * HW + px) * Ct + c) >> 2;
-      drop4(d, p.keep, p.seed, p.offset + idx4);
-    }
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float xhat = (xv[e] - mean) * rstd;
-      const float u = xhat * ga[e] + be[e];
-      const float gu = p.act ? d[e] * silu_grad_f(u) : d[e];
-      o[e] = rstd * (gu * ga[e] - m1 - xhat * m2);
-    }
-    float* dp = dxp + (size_t)px * ld;
-    if (p.accumulate) {
-      const f32x4 old = *reinterpret_cast<const f32x4*>(dp);
-      o[0] += old[0]; o[1] += old[1]; o[2] += old[2]; o[3] += old[3];
-    }
-    *reinterpret_cast<f32x4*>(dp) = o;
-  }
-}
 
 // Single-pass backward: 512 threads own (sample, 32-channel slab); each thread keeps its 16 pixels' xhat and
 // activation-gradient float4s in registers (128 VGPRs), so x and dy are read exactly once: 2 reads + 1 write.
@@ -1043,168 +934,12 @@ void gn_bwd_stream_kernel(GnBwdArgs p) {
   }
 }
 
-// The backward streaming kernel as a THIN kernel (round 5 probe): 256 threads (one wave per SIMD), <= 64 registers, 3 KB of
-// LDS, so that its blocks fit on a CU whose other resources a matrix-core block of the weight-gradient stream owns
-// (conv3x3_wgrad_f16x3_planes_kernel: 448 registers, 137 KB).  Compile-time variants instead of run-time flags (every
-// run-time branch of gn_bwd_stream_kernel costs live registers), batches of 2 pixels, and NO final reduction over the
-// samples: the per-block partial rows [B * 4][Ct] are summed by the caller (mulan_colsum_pair or the next launch).
-template <bool PLANES, int NADD, bool DROP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void gn_bwd_thin_kernel(GnBwdArgs p) {
-  if (p.seed_dev) p.seed ^= p.seed_dev[0];
-  constexpr int UB = 2;
-  __shared__ float cred[3 * 4 * 32];
-  __shared__ unsigned ured[4];
-  const int tid = threadIdx.x, quad = tid & 7, prow = tid >> 3, sp = blockIdx.z;
-  const int b = blockIdx.x, Ct = p.C1 + p.C2;
-  const int c0 = blockIdx.y * 32;
-  const int cpg = Ct / p.G, qpg = cpg >> 2, csh = 31 - __builtin_clz(cpg);
-  const bool first = c0 < p.C1;
-  const int ld = first ? p.C1 : p.C2, cs = first ? c0 : c0 - p.C1;
-  const size_t xbytes = (size_t)HW * ld * 4;
-  const int c = c0 + quad * 4, g = c >> csh;
-  const int px0 = prow + 256 * sp;
-  const float mean = p.mean[b * p.G + g], rstd = p.rstd[b * p.G + g];
-  const f32x4 ga = *reinterpret_cast<const f32x4*>(p.gamma + c);
-  const f32x4 be = *reinterpret_cast<const f32x4*>(p.beta + c);
-  float m1, m2;
-  {
-    const int nq = Ct >> 2;
-    float t1 = 0.f, t2 = 0.f;
-    for (int qq = g * qpg; qq < (g + 1) * qpg; ++qq) {
-      const float* st = p.gstats + ((size_t)b * (HW / 256) * nq + qq) * 2;
-#pragma unroll
-      for (int t = 0; t < HW / 256; ++t) { t1 += st[(size_t)t * nq * 2]; t2 += st[(size_t)t * nq * 2 + 1]; }
-    }
-    const float inv_n = 1.f / (float)(HW * cpg);
-    m1 = t1 * inv_n; m2 = t2 * inv_n;
-  }
-  float bound = 0.f;
-  if (PLANES) {
-    const int ln = tid & 63;
-    float rm = 0.f, gm = 0.f, dm = ln < 16 ? __uint_as_float(p.dymax[b * 16 + ln]) : 0.f;
-    for (int gg = ln; gg < p.G; gg += 64) rm = fmaxf(rm, p.rstd[b * p.G + gg]);
-    for (int cc = ln; cc < Ct; cc += 64) gm = fmaxf(gm, fabsf(p.gamma[cc]));
-    rm = wave_max(rm); gm = wave_max(gm); dm = wave_max(dm);
-    bound = ((sqrtf((float)(HW * cpg)) + 2.f) * (p.act ? 1.1f : 1.f)) * rm * gm * (dm / p.keep);
-  }
-  unsigned mb = 0u;
-  const float inv_keep = 1.f / p.keep;
-  if (DROP) {
-    if (p.maskbits) {
-      mb = p.maskbits[(((size_t)b * gridDim.y + blockIdx.y) * 256 + tid) * 4 + sp];
-    } else {
-      const uint32_t thr = (uint32_t)((double)p.keep * 4294967296.0);
-#pragma unroll 1
-      for (int i = 0; i < SU; ++i) {
-        const unsigned long long idx4 = (((unsigned long long)b * HW + (px0 + 32 * i)) * Ct + c) >> 2;
-        mb |= drop_bits4(thr, p.seed, p.offset + idx4) << (i * 4);
-      }
-    }
-  }
-  float psc, pinv;
-  f16x3::scale_of(__float_as_uint(bound), psc, pinv);
-  const rsrc_t xr = gn_rsrc((first ? p.x1 : p.x2) + (size_t)b * HW * ld, xbytes);
-  const rsrc_t dyr = gn_rsrc(p.dy + (size_t)b * HW * Ct, (size_t)HW * Ct * 4);
-  const float* addp = first ? p.add1 : p.add2;
-  const float* addq = first ? p.add1b : nullptr;
-  const rsrc_t a1r = gn_rsrc(NADD >= 1 && addp ? addp + (size_t)b * HW * ld : nullptr, NADD >= 1 && addp ? xbytes : 0);
-  const rsrc_t a2r = gn_rsrc(NADD >= 2 && addq ? addq + (size_t)b * HW * ld : nullptr, NADD >= 2 && addq ? xbytes : 0);
-  const rsrc_t or_ = PLANES ? gn_rsrc(p.dx1planes + (size_t)b * HW * Ct * 4, (size_t)HW * Ct * 4)
-                            : gn_rsrc((first ? p.dx1 : p.dx2) + (size_t)b * HW * ld, xbytes);
-  const unsigned xoff = (unsigned)((px0 * ld + cs + quad * 4) * 4), xstep = (unsigned)(32 * ld * 4);
-  const unsigned dyoff = (unsigned)((px0 * Ct + c) * 4), dystep = (unsigned)(32 * Ct * 4);
-  const unsigned ooff = PLANES ? (unsigned)(((c >> 4) * HW + px0) * 64 + (c & 15) * 2) : xoff;
-  const unsigned ostep = PLANES ? 32u * 64u : xstep;
-  f32x2 dg_lo = {0.f, 0.f}, dg_hi = {0.f, 0.f}, db_lo = {0.f, 0.f}, db_hi = {0.f, 0.f};
-  f32x4 csum = {0.f, 0.f, 0.f, 0.f};
-  unsigned amax = 0;
-#pragma unroll 1
-  for (int h = 0; h < SU / UB; ++h) {
-    const unsigned hx = (unsigned)(h * UB) * xstep, hd = (unsigned)(h * UB) * dystep, ho = (unsigned)(h * UB) * ostep;
-    f32x4 xh[UB], gq[UB], ad1[UB], ad2[UB];
-#pragma unroll
-    for (int i = 0; i < UB; ++i) {
-      xh[i] = gn_ld4(xr, xoff, hx + i * xstep);
-      gq[i] = gn_ld4(dyr, dyoff, hd + i * dystep);
-      if (NADD >= 1) ad1[i] = gn_ld4(a1r, xoff, hx + i * xstep);     // (NULL tensor: zero-sized resource, reads 0)
-      if (NADD >= 2) ad2[i] = gn_ld4(a2r, xoff, hx + i * xstep);
-    }
-    const unsigned mbh = mb >> (h * UB * 4);
-#pragma unroll
-    for (int i = 0; i < UB; ++i) {
-      if (DROP) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gq[i][e] = apply_bit(gq[i][e], inv_keep, mbh, i * 4 + e);
-      }
-      f32x4 o;
-      {
-        const f32x2 xa = (lo2(xh[i]) - mean) * rstd, xb = (hi2(xh[i]) - mean) * rstd;
-        f32x2 ga_ = lo2(gq[i]), gb_ = hi2(gq[i]);
-        if (p.act) {
-          const f32x2 ua = fma2(xa, lo2(ga), lo2(be)), ub = fma2(xb, hi2(ga), hi2(be));
-          const f32x2 sa = sigmoid_fast2(ua), sb = sigmoid_fast2(ub);
-          ga_ = ga_ * (sa * fma2(ua, 1.f - sa, f32x2{1.f, 1.f}));
-          gb_ = gb_ * (sb * fma2(ub, 1.f - sb, f32x2{1.f, 1.f}));
-        }
-        dg_lo = fma2(ga_, xa, dg_lo); dg_hi = fma2(gb_, xb, dg_hi);
-        db_lo += ga_; db_hi += gb_;
-        const f32x2 da = ga_ * lo2(ga), dbv = gb_ * hi2(ga);
-        const f32x2 oa = (da - m1 - xa * m2) * rstd, ob = (dbv - m1 - xb * m2) * rstd;
-        o = f32x4{oa[0], oa[1], ob[0], ob[1]};
-      }
-      if (PLANES) {
-        gn_st_planes(or_, o, bound, psc, ooff, ho + i * ostep);
-      } else {
-        if (NADD >= 1) { o[0] += ad1[i][0]; o[1] += ad1[i][1]; o[2] += ad1[i][2]; o[3] += ad1[i][3]; }
-        if (NADD >= 2) { o[0] += ad2[i][0]; o[1] += ad2[i][1]; o[2] += ad2[i][2]; o[3] += ad2[i][3]; }
-        gn_st4(or_, o, ooff, ho + i * ostep);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) amax = max(amax, __float_as_uint(o[e]) & 0x7fffffffu);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) csum[e] += o[e];
-    }
-  }
-  f32x4 dg = {dg_lo[0], dg_lo[1], dg_hi[0], dg_hi[1]}, db = {db_lo[0], db_lo[1], db_hi[0], db_hi[1]};
-#pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      dg[e] += __shfl_xor(dg[e], o, 64); db[e] += __shfl_xor(db[e], o, 64); csum[e] += __shfl_xor(csum[e], o, 64);
-    }
-  }
-  const int wave = tid >> 6, lane = tid & 63;
-  if (lane < 8) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      cred[wave * 32 + lane * 4 + e] = dg[e];
-      cred[128 + wave * 32 + lane * 4 + e] = db[e];
-      cred[256 + wave * 32 + lane * 4 + e] = csum[e];
-    }
-  }
-  if (!PLANES) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, o, 64));
-    if (lane == 0) ured[wave] = amax;
-  }
-  __syncthreads();
-  if (tid < 96) {
-    const int k = tid >> 5, ch = tid & 31;
-    const float a = (cred[k * 128 + ch] + cred[k * 128 + 32 + ch]) + (cred[k * 128 + 64 + ch] + cred[k * 128 + 96 + ch]);
-    float* dstp = k == 0 ? p.dgamma_part : (k == 1 ? p.dbeta_part : p.dxsum_part);
-    if (dstp) dstp[((size_t)b * 4 + sp) * Ct + c0 + ch] = a;
-  }
-  if (b == 0 && sp == 0 && tid < 32) {     // (probe) the totals this kernel does not form: zeroed, so that a timing run stays finite
-    if (p.dgamma) p.dgamma[c0 + tid] = 0.f;
-    if (p.dbeta) p.dbeta[c0 + tid] = 0.f;
-    if (first && p.dxsum) { p.dxsum[c0 + tid] = 0.f; if (p.dxsum2) p.dxsum2[c0 + tid] = 0.f; }
-  }
-  unsigned* mout = first ? p.dx1max : p.dx2max;
-  if (mout) {
-    const int part = (cs / 32) * 4 + sp, nparts = (ld / 32) * 4;
-    if (tid == 0) mout[b * 16 + part] = PLANES ? __float_as_uint(bound) : max(max(ured[0], ured[1]), max(ured[2], ured[3]));
-    if (part == 0 && tid >= nparts && tid < 16) mout[b * 16 + tid] = 0u;
-  }
+// the slab forward kernel, one block per (sample, 32-channel slab); tune[14] = 1 (dev A/B): plain instead of nt loads
+int launch_gn_fwd(const GnArgs& a, hipStream_t stream) {
+  const dim3 grid(a.B, (a.C1 + a.C2) / 32);
+  if (g_mulan_tune[14] == 1) hipLaunchKernelGGL(gn_fwd_kernel<false>, grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(gn_fwd_kernel<true>, grid, dim3(256), 0, stream, a);
+  MULAN_CHECK_LAUNCH();
 }
 
 }  // namespace
@@ -1222,9 +957,7 @@ MULAN_API int mulan_groupnorm_fwd_dyn(const float* x1, const float* x2, int C1, 
   if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0) return (int)hipErrorInvalidValue;
   if (ymax && Ct / 32 > 16) return (int)hipErrorInvalidValue;
   GnArgs a{x1, x2, C1, C2, gamma, beta, y, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev, nullptr, nullptr};
-  if (g_mulan_tune[14] == 1) hipLaunchKernelGGL(gn_fwd_kernel<false>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(gn_fwd_kernel<true>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  MULAN_CHECK_LAUNCH();
+  return launch_gn_fwd(a, stream);
 }
 
 // The same with the output written as the split fp16 operand planes of the f16x3 convolution that consumes it
@@ -1242,9 +975,7 @@ MULAN_API int mulan_groupnorm_fwd_planes(const float* x1, const float* x2, int C
   if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0 || Ct / 32 > 16) return (int)hipErrorInvalidValue;
   GnArgs a{x1, x2, C1, C2, gamma, beta, nullptr, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev,
            static_cast<unsigned char*>(yplanes)};
-  if (g_mulan_tune[14] == 1) hipLaunchKernelGGL(gn_fwd_kernel<false>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(gn_fwd_kernel<true>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  MULAN_CHECK_LAUNCH();
+  return launch_gn_fwd(a, stream);
 }
 
 // mulan_groupnorm_fwd_planes that also stores the dropout keep-bits it drew (keepbits: B * (C1 + C2) / 32 * 1024 unsigned,
@@ -1262,9 +993,7 @@ MULAN_API int mulan_groupnorm_fwd_planes_keepbits(const float* x1, const float* 
   if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0 || Ct / 32 > 16) return (int)hipErrorInvalidValue;
   GnArgs a{x1, x2, C1, C2, gamma, beta, nullptr, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev,
            static_cast<unsigned char*>(yplanes), keepbits};
-  if (g_mulan_tune[14] == 1) hipLaunchKernelGGL(gn_fwd_kernel<false>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(gn_fwd_kernel<true>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  MULAN_CHECK_LAUNCH();
+  return launch_gn_fwd(a, stream);
 }
 
 // Statistics pass of a GroupNorm whose normalisation happens inside its consumer (mulan_conv3x3_fwd_f16x3_gn_in: the
@@ -1280,9 +1009,7 @@ MULAN_API int mulan_groupnorm_stats(const float* x1, const float* x2, int C1, in
   const int cpg = Ct / G;
   if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0 || Ct / 32 > 16) return (int)hipErrorInvalidValue;
   GnArgs a{x1, x2, C1, C2, gamma, beta, nullptr, mean, rstd, B, G, eps, 0, 1.f, 0ull, 0ull, bound, nullptr, nullptr, nullptr, 1};
-  if (g_mulan_tune[14] == 1) hipLaunchKernelGGL(gn_fwd_kernel<false>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(gn_fwd_kernel<true>, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  MULAN_CHECK_LAUNCH();
+  return launch_gn_fwd(a, stream);
 }
 
 MULAN_API int mulan_groupnorm_fwd(const float* x1, const float* x2, int C1, int C2, const float* gamma,
@@ -1308,10 +1035,7 @@ MULAN_API int mulan_groupnorm_bwd_dyn(const float* dy, const float* x1, const fl
   GnBwdArgs a{dy, x1, x2, C1, C2, gamma, beta, mean, rstd, dx1, dx2, dgamma_part, dbeta_part,
               B, G, act, keep, seed, offset, accumulate, dx1max, dx2max, add1, add2, dxsum_part, seed_dev, nullptr, nullptr,
               nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (g_mulan_tune[2] == 1 && !dx1max && !dx2max && !add1 && !add2 && !dxsum_part)   // dev A/B: two-pass 256-thread variant
-    hipLaunchKernelGGL(gn_bwd_kernel, dim3(B, Ct / 32), dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(gn_bwd_kernel_1pass, dim3(B, Ct / 32), dim3(512), 0, stream, a);
+  hipLaunchKernelGGL(gn_bwd_kernel_1pass, dim3(B, Ct / 32), dim3(512), 0, stream, a);
   MULAN_CHECK_LAUNCH();
 }
 
@@ -1447,21 +1171,6 @@ MULAN_API int mulan_groupnorm_bwd_stream(const float* dy, const unsigned* dymax,
   // The per-block partial rows are [B * 4 / nsp][Ct]: dgamma_part / dbeta_part / dxsum_part must hold 4 B rows.
   int nsp = g_mulan_tune[21] == 1 ? 1 : (g_mulan_tune[21] == 2 ? 2 : 4);
   const int C12 = C1 > C2 ? C1 : C2;
-  if (g_mulan_tune[21] == 3 && (C12 / 32) * 4 <= 16) {
-    // (dev probe) the thin kernel: no reduction over the samples -- dgamma / dbeta / dxsum are NOT written
-    const dim3 grid(B, Ct / 32, 4);
-    const int nadd = add1b ? 2 : ((add1 || add2) ? 1 : 0);
-    const bool drop = keep < 1.f;
-#define MULAN_GN_THIN(PL, NA)                                                                                     \
-  if (drop) hipLaunchKernelGGL((gn_bwd_thin_kernel<PL, NA, true>), grid, dim3(256), 0, stream, a);                \
-  else hipLaunchKernelGGL((gn_bwd_thin_kernel<PL, NA, false>), grid, dim3(256), 0, stream, a);
-    if (dx1planes) { MULAN_GN_THIN(true, 0) }
-    else if (nadd == 2) { MULAN_GN_THIN(false, 2) }
-    else if (nadd == 1) { MULAN_GN_THIN(false, 1) }
-    else { MULAN_GN_THIN(false, 0) }
-#undef MULAN_GN_THIN
-    MULAN_CHECK_LAUNCH();
-  }
   while ((dx1max || dx2max) && (C12 / 32) * (4 / nsp) > 16) nsp *= 2;
   const dim3 grid(B, Ct / 32, 4 / nsp);
   const int ub = g_mulan_tune[22];

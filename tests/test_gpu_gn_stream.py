@@ -124,13 +124,12 @@ def reference_backward(dy, x1, x2, gamma, beta, mean, rstd, mask, keep, add1, ad
 
 @pytest.mark.parametrize("C1,C2", [(128, 0), (128, 128)])
 @pytest.mark.parametrize("keep", [1.0, 0.9])
-@pytest.mark.parametrize("tune", ["", "21=2", "21=2,22=1", "21=1,22=2", "21=3"])
+@pytest.mark.parametrize("tune", ["", "21=2", "21=2,22=1", "21=1,22=2"])
 def test_backward_stream_matches_slab_kernel_and_float64(ops, C1, C2, keep, tune):
     B, Ct = 3, C1 + C2
     for kv in filter(None, tune.split(",")):
         k, v = kv.split("=")
         ops.call("mulan_set_tuning", int(k), int(v))
-    thin = tune == "21=3"
     x1, x2, gamma, beta = make(B, C1, C2, 5)
     dy = torch.randn(B, HW, Ct, device="cuda") * 1e-2
     dy[0, 7, 3] = 1.0
@@ -162,10 +161,10 @@ def test_backward_stream_matches_slab_kernel_and_float64(ops, C1, C2, keep, tune
                      p(parts[0]), p(parts[1]), B, HW, G, 1, keep, 77, 128, None, p(mx1), p(mx2), p(add1), None, p(add1b), p(parts[2]),
                      p(dg), p(db), p(sink), None, p(tick), ops.stream())
         dx = dx1 if dx2 is None else torch.cat((dx1, dx2), -1)
-        return dx, dg, db, sink, mx1, mx2, parts
+        return dx, dg, db, sink, mx1, mx2
 
-    dx_s, dg_s, db_s, sink_s, mx1_s, mx2_s, _ = run(False)
-    dx_t, dg_t, db_t, sink_t, mx1_t, mx2_t, parts = run(True)
+    dx_s, dg_s, db_s, sink_s, mx1_s, mx2_s = run(False)
+    dx_t, dg_t, db_t, sink_t, mx1_t, mx2_t = run(True)
     torch.cuda.synchronize()
     assert int(tick.abs().sum()) == 0
     scale = float(ref_dx.abs().max())
@@ -174,10 +173,6 @@ def test_backward_stream_matches_slab_kernel_and_float64(ops, C1, C2, keep, tune
     assert torch.equal(mx1_t.view(B, 16).amax(1), dx_t[..., :C1].abs().amax((1, 2)).view(torch.int32))
     if C2:
         assert torch.equal(mx2_t.view(B, 16).amax(1), dx_t[..., C1:].abs().amax((1, 2)).view(torch.int32))
-    if thin:
-        # the thin form leaves the per-block partial rows [B * 4][Ct]: their sums are the totals
-        dg_t, db_t = parts[0].double().sum(0).float(), parts[1].double().sum(0).float()
-        sink_t = parts[2].double().sum(0).float()[:C1]
     for got, slab, ref in ((dg_t, dg_s, ref_dg), (db_t, db_s, ref_db)):
         s = float(ref.abs().max())
         assert float((got.double() - ref).abs().max()) / s <= 2.0 * float((slab.double() - ref).abs().max()) / s + 2e-6
@@ -186,7 +181,7 @@ def test_backward_stream_matches_slab_kernel_and_float64(ops, C1, C2, keep, tune
 
 
 @pytest.mark.parametrize("keep", [1.0, 0.9])
-@pytest.mark.parametrize("tune", ["", "21=2,22=1", "21=3"])
+@pytest.mark.parametrize("tune", ["", "21=2,22=1"])
 def test_backward_stream_planes_output(ops, keep, tune):
     """dx as split planes (the gradient norm2 hands to conv1): the planes of mulan_groupnorm_bwd_fused_planes to rounding,
     the same bound, the stored keep-bits instead of the re-draw give the same planes bit for bit"""

@@ -32,7 +32,7 @@ F32_EPS = float(np.finfo(np.float32).eps)
 INVALID = 1                      # hipErrorInvalidValue
 SEED, OFFSET = 0x1234ABCD5678, 5 << 34
 POISON_F, POISON_I = -7.0e37, 0x7F0F0F0F
-TUNE_KEYS = (2, 14, 20, 21, 22)
+TUNE_KEYS = (14, 20, 21, 22)
 
 # exported entry point -> the float64-referenced test here that calls it (tests/test_groupnorm_table.py holds it to the header)
 COVERAGE = {
@@ -73,9 +73,7 @@ def set_tune(ops, k, v):
 def z_blocks(tune, slabs, fits=True):
     """blocks per slab of a streaming launch: 1 (default), 4 / 2 under tune = 1 / 2, halved until (slabs) x (blocks) fits
     the 16 entries of a maxima array (where one is written)"""
-    z = {1: 4, 2: 2, 3: 4}.get(tune, 1)
-    if tune == 3 and slabs * 4 > 16:
-        z = 1                                                         # (the thin kernel is not taken)
+    z = {1: 4, 2: 2}.get(tune, 1)
     while fits and slabs * z > 16:
         z //= 2
     return z
@@ -390,7 +388,7 @@ def bwd_bound(c):
         float(np.float32(c.keep))
 
 
-def check_bwd(tag, c, o, *, adds=(), planes=False, totals=False, thin=False):
+def check_bwd(tag, c, o, *, adds=(), planes=False, totals=False):
     """what a backward launch left, against float64.  The channel sums of dx (dxsum_part, dxsum) are held to their own
     reference values where the skip-path gradients make them sums that do not cancel (add1, and add2 for a concat): the
     channel sums of a bare GroupNorm gradient add up to zero over every group, so single ones come arbitrarily close to it"""
@@ -423,7 +421,7 @@ def check_bwd(tag, c, o, *, adds=(), planes=False, totals=False, thin=False):
         assert written(o["dxsp"][:B * z]), tag
         if sums_ok:
             check_each(tag + " dxsum_part", fold(o["dxsp"]), ref.sum(1))
-    if totals and not thin:
+    if totals:
         assert written(o["dg"]) and written(o["db"]), tag
         check_each(tag + " dgamma", o["dg"], c.dgamma)
         check_each(tag + " dbeta", o["db"], c.dbeta)
@@ -794,14 +792,13 @@ def test_dropout_keepbits_feed_the_planes_backward(ops):
 
 
 # ------------------------------------------------------------------------------------------------ F: variants
-VARIANTS = ["14=1", "2=1", "20=1", "20=2", "21=1", "21=2", "21=3", "22=1", "22=2", "21=1,22=2"]
+VARIANTS = ["14=1", "20=1", "20=2", "21=1", "21=2", "22=1", "22=2", "21=1,22=2"]
 
 
 @pytest.mark.parametrize("C1,C2", [(128, 128), (96, 32)])
 @pytest.mark.parametrize("tune", VARIANTS)
 def test_dev_variants_hold_the_same_bars(ops, C1, C2, tune):
-    """F: the kernels behind tune[14] (plain loads), tune[2] (two-pass backward), tune[20] / tune[21] (quarters of a slab
-    per block; 21 = 3: the thin kernel, which leaves the reduction over the samples to its caller) and tune[22] (load
+    """F: the kernels behind tune[14] (plain loads), tune[20] / tune[21] (quarters of a slab per block) and tune[22] (load
     batches) on the scales case, same float64 bars; bit for bit the default where the code promises the same order:
     tune[14] (the same kernel but for the load policy: everything) and tune[20] (mean / rstd from the partial sums in a
     fixed order, the keep-bits)."""
@@ -817,25 +814,17 @@ def test_dev_variants_hold_the_same_bars(ops, C1, C2, tune):
     if 14 in keys:
         outs = forward_entry_points(ops, c)
         assert all(torch.equal(outs["dyn"][k], base_f[k]) for k in ("y", "mean", "rstd", "ymax"))
-    elif 2 in keys:       # the two-pass kernel takes no by-products and no skip-path gradients
-        o = run_bwd(ops, c, "mulan_groupnorm_bwd_dyn", maxima=False, sums=False)
-        check_bwd("bwd_dyn[two-pass]", c, o)
-        o = run_bwd(ops, c, "mulan_groupnorm_bwd_dyn", maxima=False, sums=False, accumulate=True)
-        check_bwd("bwd_dyn[two-pass, acc]", c, o)
     elif 20 in keys:      # statistics from the partial sums in a fixed order, the keep-bits are integers: the same bits
         outs = forward_entry_points(ops, c)
         s = outs["stream_planes"]
         assert all(torch.equal(s[k], base_s[k]) for k in ("mean", "rstd", "kb"))
         assert torch.equal(s["ymax"].amax(1), base_s["ymax"].amax(1))
     else:
-        thin = tune == "21=3"
         o = run_bwd(ops, c, "mulan_groupnorm_bwd_stream", adds=adds)
-        check_bwd("bwd_stream[" + tune + "]", c, o, adds=adds, totals=True, thin=thin)
+        check_bwd("bwd_stream[" + tune + "]", c, o, adds=adds, totals=True)
         assert torch.equal(o["mx1"].amax(1), bits_of_max(o["dx"][..., :C1]))
-        if thin:          # (the probe zeroes the totals it does not form)
-            assert float(o["dg"].abs().max()) == 0 and float(o["db"].abs().max()) == 0
         o = run_bwd(ops, c, "mulan_groupnorm_bwd_stream", adds=adds, maxima=False)      # no maxima array: nothing caps the z blocks
-        check_bwd("bwd_stream[" + tune + ", no maxima]", c, o, adds=adds, totals=True, thin=thin)
+        check_bwd("bwd_stream[" + tune + ", no maxima]", c, o, adds=adds, totals=True)
 
 
 # ------------------------------------------------------------------------------------------------ G: past 2^31 bytes
