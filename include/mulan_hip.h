@@ -559,6 +559,22 @@ int mulan_schedule_moments(const float* a, const float* b, const float* c, int B
  * hipErrorInvalidValue for a NULL pointer, B < 1, M < 1, gamma_min >= gamma_max. */
 int mulan_schedule_invert(const float* m, int B, const double* targets, int M, double gamma_min, double gamma_max,
                           float* t_out, mulan_stream_t stream);
+/* The schedules of E embeddings on a grid of T times, and their summaries over each embedding's d sub-pixels, in one
+ * launch (the data of notebook_utils.noise_schedule_per_embedding, plot_heat_map and plot_histogram, :554-667).
+ * a, b, c [E][d] as mulan_poly_gamma_fwd takes them, t [T] (any order, repeats allowed); each output may be NULL, not all:
+ *   gamma_out [E][T][d]  gamma_i(t) = gamma_min + (gamma_max - gamma_min) P_i(t) / S_i; S as mulan_schedule_moments forms
+ *                        it; t = 0 gives gamma_min bit for bit
+ *   stats_out [E][T][8]  mean, population standard deviation (about the mean; exactly 0 where all values are equal), min,
+ *                        max, the means of the three channels (sub-pixel i is channel i % 3), the mean of sigmoid(gamma)
+ *   hist_out [E][T][bins] the number of sub-pixels with min(bins - 1, (int)((gamma - gamma_min) * s)) == k, where
+ *                        s = (float)bins / (gamma_max - gamma_min) is formed once, in fp32, by this function on the host
+ * With gamma_out NULL no curve is written anywhere.  Every sum is taken in one fixed order (no floating-point atomics):
+ * the same bits on every run.  a, b, c, gamma_out and stats_out must be 16-byte aligned.
+ * hipErrorInvalidValue, before anything is launched, for a NULL input, all three outputs NULL, d != 3072, E < 1, T < 1,
+ * bins outside 1..256 with hist_out given, gamma_min >= gamma_max, a misaligned pointer. */
+int mulan_schedule_curves(const float* a, const float* b, const float* c, int E, int d, const float* t, int T,
+                          float gamma_min, float gamma_max, float* gamma_out, float* stats_out, int* hist_out, int bins,
+                          mulan_stream_t stream);
 /* discrete-time (T > 0) loss weight w = T * expm1(gamma_t - gamma_s) (model_mulan_epsilon.py:348-355) */
 int mulan_expm1_weight_fwd(const float* gt, const float* gs, float* w, size_t n, float T, mulan_stream_t stream);
 int mulan_expm1_weight_bwd(const float* gt, const float* gs, const float* dw, float* dgt, float* dgs, size_t n,

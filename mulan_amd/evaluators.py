@@ -537,3 +537,175 @@ def eval_bpd_ode(experiment, config, deterministic_noise, hutchinson_type, dequa
             print(f'[Iter {i}] Test BPD:{mean}')
         bpd_means.append(mean)
     return float(np.mean(bpd_means))
+
+
+# ------------------------------------------------------------------ the learned noise schedule (notebook_utils.py:554-711)
+SCHEDULE_BUFFER_BYTES = 1 << 30   # device budget of one launch's outputs (1 GiB): the embeddings go through in chunks of it
+REC709 = (0.2125, 0.7154, 0.0721)            # the luminance weights of skimage.color.rgb2gray
+
+
+def _schedule_inputs(experiment, embeddings, time_steps):
+    """(embeddings fp32 [E, latent_size] on the device, times fp32 [T] on the device) or ValueError"""
+    model = experiment.model
+    if not hasattr(model, "deterministic_embedding"):
+        raise ValueError("the schedule per embedding needs a MuLAN model (model_vdm.VDM has one scalar schedule and no "
+                         "latent embedding)")
+    if not torch.is_tensor(embeddings):
+        embeddings = torch.as_tensor(np.asarray(embeddings, dtype=np.float32))
+    L = model.config.latent_size
+    if embeddings.dim() != 2 or embeddings.shape[0] < 1 or embeddings.shape[1] != L:
+        raise ValueError(f"embeddings are [E, {L}] with E >= 1, got {list(embeddings.shape)}")
+    if time_steps is None:
+        time_steps = np.linspace(0.0, 1.0, 128)
+    if torch.is_tensor(time_steps):
+        time_steps = time_steps.detach().cpu().numpy()
+    t = np.asarray(time_steps, dtype=np.float32).reshape(-1)
+    if t.size < 1 or not np.isfinite(t).all() or t.min() < 0.0 or t.max() > 1.0:
+        raise ValueError("time_steps are finite times in [0, 1], at least one")
+    dev = experiment.device
+    return embeddings.to(device=dev, dtype=torch.float32).contiguous(), torch.from_numpy(t).to(dev)
+
+
+def _schedule_chunks(experiment, emb, bytes_per_embedding):
+    """(first index, a, b, c) of consecutive chunks of the embeddings, each chunk's outputs within SCHEDULE_BUFFER_BYTES;
+    the coefficient MLP (poly_coefficients) runs once per embedding"""
+    from .model import poly_coefficients
+    step = max(1, SCHEDULE_BUFFER_BYTES // bytes_per_embedding)
+    for i in range(0, emb.shape[0], step):
+        with torch.no_grad():
+            yield (i, *poly_coefficients(experiment.orig_params["gamma"], emb[i:i + step].contiguous()))
+
+
+def noise_schedule_per_embedding(experiment, embeddings, time_steps=None):
+    """notebook_utils.noise_schedule_per_embedding (:554-568): a list of E numpy arrays [T, 3072], gamma of every
+    sub-pixel at the T times (default linspace(0, 1, 128); any T -- the reference's repeat(128) ties T to 128) under each
+    row of `embeddings` [E, latent_size].  One launch of mulan_schedule_curves per chunk of embeddings."""
+    from . import ops
+    emb, t = _schedule_inputs(experiment, embeddings, time_steps)
+    cfg = experiment.model.config
+    out = []
+    for _, a, b, c in _schedule_chunks(experiment, emb, t.numel() * 3072 * 4):
+        gamma, _, _ = ops.schedule_curves(a, b, c, t, cfg.gamma_min, cfg.gamma_max)
+        out.extend(gamma.cpu().numpy())
+    return out
+
+
+def noise_schedule_summary(experiment, embeddings, time_steps=None, bins=100):
+    """What the reference's schedule plots show, without a curve leaving the device: a dict of numpy arrays -- mean, std
+    (population), min, max, sigma2_mean (the mean of sigmoid(gamma)), each [E, T], over the 3072 sub-pixels of embedding e
+    at time t; channel_mean [E, T, 3]; hist [E, T, bins], the counts over [gamma_min, gamma_max] in equal bins (what
+    plot_histogram draws); time_steps [T]; between [T], the standard deviation over the embeddings of `mean`: zero for a
+    schedule that does not look at its input."""
+    from . import ops
+    emb, t = _schedule_inputs(experiment, embeddings, time_steps)
+    if not 1 <= int(bins) <= 256:
+        raise ValueError(f"bins lies in 1..256, got {bins}")
+    cfg = experiment.model.config
+    stats, hist = [], []
+    for _, a, b, c in _schedule_chunks(experiment, emb, t.numel() * (8 + int(bins)) * 4):
+        _, s, h = ops.schedule_curves(a, b, c, t, cfg.gamma_min, cfg.gamma_max, curves=False, stats=True, bins=int(bins))
+        stats.append(s.cpu().numpy())
+        hist.append(h.cpu().numpy())
+    s = np.concatenate(stats)
+    return dict(mean=s[..., 0], std=s[..., 1], min=s[..., 2], max=s[..., 3], channel_mean=s[..., 4:7],
+                sigma2_mean=s[..., 7], hist=np.concatenate(hist), time_steps=t.cpu().numpy(),
+                between=s[..., 0].astype(np.float64).std(axis=0))
+
+
+def get_embedding(batch_size=2, latent_size=50, shift=0):
+    """notebook_utils.get_embedding (:582-586): 15 ones then zeros, rolled by `shift`; fp32 [batch_size, latent_size]"""
+    emb = torch.zeros((batch_size, latent_size), dtype=torch.float32)
+    emb[:, :15] = 1.0
+    return torch.roll(emb, shifts=shift, dims=1)
+
+
+def heat_map_panels(schedule, cols=10, crop=2):
+    """The data of notebook_utils.plot_heat_map (:630-651) for one schedule [T, 3072]: fp [cols, 32 - 2 crop,
+    32 - 2 crop]; panel k is the row int(T k / cols) as a (32, 32, 3) image, cropped, min-max normalised (a constant
+    panel: zeros) and turned to luminance with the Rec. 709 weights of skimage.color.rgb2gray"""
+    ns = np.asarray(schedule, dtype=np.float64)
+    if ns.ndim != 2 or ns.shape[1] != 3072 or cols < 1 or not 0 <= crop < 16:
+        raise ValueError(f"a schedule is [T, 3072], cols >= 1, 0 <= crop < 16; got {list(ns.shape)}, {cols}, {crop}")
+    panels = np.zeros((cols, 32 - 2 * crop, 32 - 2 * crop))
+    for k in range(cols):
+        p = ns[int(ns.shape[0] * k / cols)].reshape(32, 32, 3)[crop:32 - crop, crop:32 - crop]
+        span = p.max() - p.min()
+        if span > 0:
+            panels[k] = ((p - p.min()) / span) @ np.asarray(REC709)
+    return panels
+
+
+class Clustering:
+    """notebook_utils.Clustering (:669-695) without the drawing: embeddings whose dot product exceeds `threshold` times
+    the largest one belong together"""
+
+    def __init__(self, images, embeddings, threshold=0.8):
+        self.images = images
+        emb = embeddings.detach().cpu().numpy() if torch.is_tensor(embeddings) else np.asarray(embeddings)
+        self.dotp = emb.astype(np.float64) @ emb.astype(np.float64).T
+        self.threshold = threshold * np.max(self.dotp)
+
+    def clusters(self, cluster_count=20, cluster_size_max=10):
+        """a list of index lists: for each of the first `cluster_count` embeddings i that have a neighbour, i and then
+        its neighbours in index order, `cluster_size_max` entries at the most (print_clusters' rule)"""
+        near = self.dotp > self.threshold
+        out = []
+        for i in np.where(near.sum(axis=0) > 1)[0][:cluster_count]:
+            cluster = [int(i)]
+            for j in np.where(near[i])[0]:
+                if j == i:
+                    continue
+                cluster.append(int(j))
+                if len(cluster) == cluster_size_max:
+                    break
+            out.append(cluster)
+        return out
+
+
+def _time_ticks(plt, T):
+    plt.xticks((np.linspace(0, 1, 10) * T).astype(int), ['{:.1f}'.format(i) for i in np.linspace(0, 1, 10)])
+    plt.ylabel(r'$\gamma(t)$')
+    plt.xlabel('$t$')
+
+
+def plot_noise_schedule(noise_schedules, epoch=''):
+    """notebook_utils.plot_noise_schedule (:571-579): every sub-pixel's curve of the first schedule"""
+    import matplotlib.pyplot as plt
+    fig = plt.figure()
+    plt.plot(noise_schedules[0])
+    plt.title(f'Noise Schedule per pixel for an input epoch:{epoch}')
+    _time_ticks(plt, len(noise_schedules[0]))
+    return fig
+
+
+def plot_heat_map(noise_schedules, count=3, cols=10):
+    """notebook_utils.plot_heat_map (:630-651): heat_map_panels of the first `count` schedules"""
+    import matplotlib.pyplot as plt
+    figs = []
+    for ns in noise_schedules[:count]:
+        fig = plt.figure(figsize=(6, 6))
+        for k, panel in enumerate(heat_map_panels(ns, cols)):
+            fig.add_subplot(1, cols, k + 1)
+            plt.imshow(panel, cmap='hot', interpolation='nearest')
+            plt.title('t={:.1f}'.format(k / cols), fontsize=8)
+            plt.xticks([], [])
+            plt.yticks([], [])
+        figs.append(fig)
+    return figs
+
+
+def plot_histogram(hist, count=3, cols=5):
+    """notebook_utils.plot_histogram (:655-666) from noise_schedule_summary's `hist` [E, T, bins] (or the summary itself):
+    for the first `count` embeddings, the histogram at the rows int(T k / cols)"""
+    import matplotlib.pyplot as plt
+    hist = np.asarray(hist['hist'] if isinstance(hist, dict) else hist)
+    figs = []
+    for h in hist[:count]:
+        fig = plt.figure(figsize=(cols, 1))
+        for k in range(cols):
+            fig.add_subplot(1, cols, k + 1)
+            plt.bar(np.arange(h.shape[1]), h[int(h.shape[0] * k / cols)], width=1.0)
+            plt.xticks([])
+            plt.yticks([])
+        figs.append(fig)
+    return figs

@@ -87,6 +87,7 @@ SIGNATURES = {
     "mulan_poly_gamma_bwd": [P, P, P, P, P, P, P, P, P, I, I, F, F, P],
     "mulan_schedule_moments": [P, P, P, I, I, P, P],
     "mulan_schedule_invert": [P, I, P, I, D, D, P, P],
+    "mulan_schedule_curves": [P, P, P, I, I, P, I, F, F, P, P, P, I, P],
     "mulan_expm1_weight_fwd": [P, P, P, Z, F, P],
     "mulan_expm1_weight_bwd": [P, P, P, P, P, Z, F, P],
     "mulan_qsample_fwd": [P, P, P, P, I, P, P, P, P, P, P, P, P, I, I, P],

@@ -2297,6 +2297,33 @@ def schedule_invert(m, targets, gmin, gmax):
     return out
 
 
+def schedule_curves(a, b, c, t, gmin, gmax, *, curves=True, stats=False, bins=None):
+    """(gamma | None, stats | None, hist | None) of E embeddings at the T times of `t` (fp32 [T], any order), one launch
+    (mulan_schedule_curves); a, b, c fp32 [E, 3072].  curves: gamma fp32 [E, T, 3072].  stats: fp32 [E, T, 8] over the
+    sub-pixels -- mean, population standard deviation, min, max, the three channel means, the mean of sigmoid(gamma).
+    bins (1..256): int32 [E, T, bins], the histogram over [gmin, gmax] in `bins` equal bins.  Without curves none is
+    written."""
+    a, b, c, t = _c(a), _c(b), _c(c), _c(t)
+    if not (a.dtype == b.dtype == c.dtype == torch.float32) or a.dim() != 2 or a.shape[1] != D or a.shape[0] < 1 \
+            or b.shape != a.shape or c.shape != a.shape:
+        raise ValueError(f"schedule_curves: a, b, c are fp32 [E, {D}]; got {[tuple(x.shape) for x in (a, b, c)]}")
+    if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < 1 or t.device != a.device:
+        raise ValueError(f"schedule_curves: t is an fp32 [T] tensor on {a.device}; got {t.dtype} {tuple(t.shape)}")
+    if not (curves or stats or bins is not None):
+        raise ValueError("schedule_curves: nothing asked for (curves, stats and bins are all off)")
+    if bins is not None and not 1 <= int(bins) <= 256:
+        raise ValueError(f"schedule_curves: bins lies in 1..256, got {bins}")
+    if not float(gmin) < float(gmax):
+        raise ValueError(f"schedule_curves: gmin < gmax, got {gmin}, {gmax}")
+    E, T = a.shape[0], t.numel()
+    gamma = torch.empty((E, T, D), device=a.device, dtype=torch.float32) if curves else None
+    st = torch.empty((E, T, 8), device=a.device, dtype=torch.float32) if stats else None
+    hist = torch.empty((E, T, int(bins)), device=a.device, dtype=torch.int32) if bins is not None else None
+    call("mulan_schedule_curves", ptr(a), ptr(b), ptr(c), E, D, ptr(t), T, float(gmin), float(gmax), ptr(gamma), ptr(st),
+         ptr(hist), int(bins) if bins is not None else 0, stream())
+    return gamma, st, hist
+
+
 # ----------------------------------------------------------------------------- exact-likelihood ODE (eval only)
 def topk_hard(logits, k):
     """(k-hot embedding of the plain logits, KL(softmax(logits) || uniform)): notebook_utils.logits_to_embeddings and
