@@ -942,6 +942,23 @@ int launch_gn_fwd(const GnArgs& a, hipStream_t stream) {
   MULAN_CHECK_LAUNCH();
 }
 
+// the slab backward kernel, one block per (sample, 32-channel slab)
+int launch_gn_bwd(const GnBwdArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(gn_bwd_kernel_1pass, dim3(a.B, (a.C1 + a.C2) / 32), dim3(512), 0, stream, a);
+  MULAN_CHECK_LAUNCH();
+}
+
+// The shape every entry point of the family takes: 32 x 32 pixels, whole groups of 4, 8, 16 or 32 channels, both inputs
+// of a concat whole 32-channel slabs.  maxima16: a [B][16] maxima array with one entry per slab of C1 + C2 is involved.
+// What else an entry point requires (pointers, keep ranges, its own caps) stands in the entry point.
+bool gn_shape_ok(int C1, int C2, int B, int hw, int G, bool maxima16) {
+  const int Ct = C1 + C2;
+  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0) return false;
+  const int cpg = Ct / G;
+  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0) return false;
+  return !(maxima16 && Ct / 32 > 16);
+}
+
 }  // namespace
 
 // seed_dev (optional, device memory): the dropout seed is `seed ^ seed_dev[0]`, read by the kernel when it runs -- a
@@ -951,12 +968,10 @@ MULAN_API int mulan_groupnorm_fwd_dyn(const float* x1, const float* x2, int C1, 
                                       float eps, int act, float keep, unsigned long long seed,
                                       unsigned long long offset, const unsigned long long* seed_dev, unsigned* ymax,
                                       hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0) return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0) return (int)hipErrorInvalidValue;
-  if (ymax && Ct / 32 > 16) return (int)hipErrorInvalidValue;
-  GnArgs a{x1, x2, C1, C2, gamma, beta, y, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev, nullptr, nullptr};
+  if (!gn_shape_ok(C1, C2, B, hw, G, ymax != nullptr)) return (int)hipErrorInvalidValue;
+  const GnArgs a{.x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .y = y, .mean = mean, .rstd = rstd,
+                 .B = B, .G = G, .eps = eps, .act = act, .keep = keep, .seed = seed, .offset = offset, .ymax = ymax,
+                 .seed_dev = seed_dev};
   return launch_gn_fwd(a, stream);
 }
 
@@ -969,12 +984,10 @@ MULAN_API int mulan_groupnorm_fwd_planes(const float* x1, const float* x2, int C
                                          float eps, int act, float keep, unsigned long long seed,
                                          unsigned long long offset, const unsigned long long* seed_dev, unsigned* ymax,
                                          hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0 || !yplanes || !ymax || !(keep > 0.f)) return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0 || Ct / 32 > 16) return (int)hipErrorInvalidValue;
-  GnArgs a{x1, x2, C1, C2, gamma, beta, nullptr, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev,
-           static_cast<unsigned char*>(yplanes)};
+  if (!gn_shape_ok(C1, C2, B, hw, G, true) || !yplanes || !ymax || !(keep > 0.f)) return (int)hipErrorInvalidValue;
+  const GnArgs a{.x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .mean = mean, .rstd = rstd,
+                 .B = B, .G = G, .eps = eps, .act = act, .keep = keep, .seed = seed, .offset = offset, .ymax = ymax,
+                 .seed_dev = seed_dev, .yplanes = static_cast<unsigned char*>(yplanes)};
   return launch_gn_fwd(a, stream);
 }
 
@@ -986,13 +999,11 @@ MULAN_API int mulan_groupnorm_fwd_planes_keepbits(const float* x1, const float* 
                                                   int G, float eps, int act, float keep, unsigned long long seed,
                                                   unsigned long long offset, const unsigned long long* seed_dev,
                                                   unsigned* ymax, unsigned* keepbits, hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0 || !yplanes || !ymax || !keepbits || !(keep > 0.f) || !(keep < 1.f))
+  if (!gn_shape_ok(C1, C2, B, hw, G, true) || !yplanes || !ymax || !keepbits || !(keep > 0.f) || !(keep < 1.f))
     return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0 || Ct / 32 > 16) return (int)hipErrorInvalidValue;
-  GnArgs a{x1, x2, C1, C2, gamma, beta, nullptr, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev,
-           static_cast<unsigned char*>(yplanes), keepbits};
+  const GnArgs a{.x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .mean = mean, .rstd = rstd,
+                 .B = B, .G = G, .eps = eps, .act = act, .keep = keep, .seed = seed, .offset = offset, .ymax = ymax,
+                 .seed_dev = seed_dev, .yplanes = static_cast<unsigned char*>(yplanes), .maskbits = keepbits};
   return launch_gn_fwd(a, stream);
 }
 
@@ -1004,11 +1015,9 @@ MULAN_API int mulan_groupnorm_fwd_planes_keepbits(const float* x1, const float* 
 MULAN_API int mulan_groupnorm_stats(const float* x1, const float* x2, int C1, int C2, const float* gamma, const float* beta,
                                     float* mean, float* rstd, unsigned* bound, int B, int hw, int G, float eps,
                                     hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0 || !bound || !mean || !rstd) return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0 || Ct / 32 > 16) return (int)hipErrorInvalidValue;
-  GnArgs a{x1, x2, C1, C2, gamma, beta, nullptr, mean, rstd, B, G, eps, 0, 1.f, 0ull, 0ull, bound, nullptr, nullptr, nullptr, 1};
+  if (!gn_shape_ok(C1, C2, B, hw, G, true) || !bound || !mean || !rstd) return (int)hipErrorInvalidValue;
+  const GnArgs a{.x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .mean = mean, .rstd = rstd,
+                 .B = B, .G = G, .eps = eps, .keep = 1.f, .ymax = bound, .stats_only = 1};
   return launch_gn_fwd(a, stream);
 }
 
@@ -1020,6 +1029,7 @@ MULAN_API int mulan_groupnorm_fwd(const float* x1, const float* x2, int C1, int 
                                  nullptr, ymax, stream);
 }
 
+// dx1max / dx2max (optional, [B][16] each) are per input: each is capped at 16 slabs of its own input.
 MULAN_API int mulan_groupnorm_bwd_dyn(const float* dy, const float* x1, const float* x2, int C1, int C2,
                                       const float* gamma, const float* beta, const float* mean, const float* rstd,
                                       float* dx1, float* dx2, float* dgamma_part, float* dbeta_part, int B, int hw,
@@ -1027,23 +1037,21 @@ MULAN_API int mulan_groupnorm_bwd_dyn(const float* dy, const float* x1, const fl
                                       const unsigned long long* seed_dev, int accumulate, unsigned* dx1max,
                                       unsigned* dx2max, const float* add1, const float* add2, float* dxsum_part,
                                       hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0) return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0) return (int)hipErrorInvalidValue;
-  if ((dx1max && C1 / 32 > 16) || (dx2max && C2 / 32 > 16)) return (int)hipErrorInvalidValue;
-  GnBwdArgs a{dy, x1, x2, C1, C2, gamma, beta, mean, rstd, dx1, dx2, dgamma_part, dbeta_part,
-              B, G, act, keep, seed, offset, accumulate, dx1max, dx2max, add1, add2, dxsum_part, seed_dev, nullptr, nullptr,
-              nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(gn_bwd_kernel_1pass, dim3(B, Ct / 32), dim3(512), 0, stream, a);
-  MULAN_CHECK_LAUNCH();
+  if (!gn_shape_ok(C1, C2, B, hw, G, false) || (dx1max && C1 / 32 > 16) || (dx2max && C2 / 32 > 16))
+    return (int)hipErrorInvalidValue;
+  const GnBwdArgs a{.dy = dy, .x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .mean = mean,
+                    .rstd = rstd, .dx1 = dx1, .dx2 = dx2, .dgamma_part = dgamma_part, .dbeta_part = dbeta_part, .B = B, .G = G,
+                    .act = act, .keep = keep, .seed = seed, .offset = offset, .accumulate = accumulate, .dx1max = dx1max,
+                    .dx2max = dx2max, .add1 = add1, .add2 = add2, .dxsum_part = dxsum_part, .seed_dev = seed_dev};
+  return launch_gn_bwd(a, stream);
 }
 
 // mulan_groupnorm_bwd_dyn + the final reduction over the samples inside the launch: dgamma / dbeta [C1 + C2] receive the
 // totals (dgamma_part / dbeta_part [B, C1 + C2] stay the scratch for the per-sample partials), dxsum (optional, [C1]) the
 // sum over samples of dxsum_part's x1 columns -- the bias gradient of the convolution whose output gradient dx1 is --
 // and dxsum2 (optional) a second copy of it (the bias of a shortcut layer that sees the same gradient).
-// tickets: [16] unsigned, zero before the first launch on a stream (every launch leaves them zero again).
+// tickets: [16] unsigned, zero before the first launch on a stream (every launch leaves them zero again); one entry per
+// slab, hence 16 slabs of C1 + C2 at most with or without maxima arrays.
 // add1b (optional, like x1): a second outside gradient of x1, dx1 = (dx1 + add1) + add1b (the skip-connection gradient of a
 // U-Net block output whose other consumer is this GroupNorm).
 MULAN_API int mulan_groupnorm_bwd_fused(const float* dy, const float* x1, const float* x2, int C1, int C2,
@@ -1054,17 +1062,15 @@ MULAN_API int mulan_groupnorm_bwd_fused(const float* dy, const float* x1, const 
                                         const float* add1, const float* add2, const float* add1b, float* dxsum_part,
                                         float* dgamma, float* dbeta, float* dxsum, float* dxsum2, unsigned* tickets,
                                         hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0 || !tickets || !dgamma || !dbeta || !dgamma_part || !dbeta_part ||
-      (dxsum && !dxsum_part) || (dxsum2 && !dxsum) || Ct / 32 > 16)
+  if (!gn_shape_ok(C1, C2, B, hw, G, true) || !tickets || !dgamma || !dbeta || !dgamma_part || !dbeta_part ||
+      (dxsum && !dxsum_part) || (dxsum2 && !dxsum))
     return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0) return (int)hipErrorInvalidValue;
-  GnBwdArgs a{dy, x1, x2, C1, C2, gamma, beta, mean, rstd, dx1, dx2, dgamma_part, dbeta_part,
-              B, G, act, keep, seed, offset, 0, dx1max, dx2max, add1, add2, dxsum_part, seed_dev, tickets, dgamma, dbeta,
-              dxsum, dxsum2, nullptr, nullptr, nullptr, add1b};
-  hipLaunchKernelGGL(gn_bwd_kernel_1pass, dim3(B, Ct / 32), dim3(512), 0, stream, a);
-  MULAN_CHECK_LAUNCH();
+  const GnBwdArgs a{.dy = dy, .x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .mean = mean,
+                    .rstd = rstd, .dx1 = dx1, .dx2 = dx2, .dgamma_part = dgamma_part, .dbeta_part = dbeta_part, .B = B, .G = G,
+                    .act = act, .keep = keep, .seed = seed, .offset = offset, .dx1max = dx1max, .dx2max = dx2max,
+                    .add1 = add1, .add2 = add2, .dxsum_part = dxsum_part, .seed_dev = seed_dev, .tickets = tickets,
+                    .dgamma = dgamma, .dbeta = dbeta, .dxsum = dxsum, .dxsum2 = dxsum2, .add1b = add1b};
+  return launch_gn_bwd(a, stream);
 }
 
 // mulan_groupnorm_bwd_fused for a single input whose gradient feeds ONLY the f16x3 kernels of the convolution in front
@@ -1083,17 +1089,17 @@ MULAN_API int mulan_groupnorm_bwd_fused_planes(const float* dy, const unsigned* 
                                                unsigned* dxmax, float* dxsum_part, float* dgamma, float* dbeta,
                                                float* dxsum, float* dxsum2, unsigned* tickets,
                                                const unsigned* keepbits, hipStream_t stream) {
-  if (hw != HW || B <= 0 || G <= 0 || C % G != 0 || !tickets || !dgamma || !dbeta || !dgamma_part || !dbeta_part ||
-      !dxplanes || !dymax || !dxmax || !(keep > 0.f) || (dxsum && !dxsum_part) || (dxsum2 && !dxsum) || C / 32 > 16 ||
-      C % 32 != 0 || (size_t)B * HW * C * 4 >= 0x80000000ull)
+  if (!gn_shape_ok(C, 0, B, hw, G, true) || !tickets || !dgamma || !dbeta || !dgamma_part || !dbeta_part || !dxplanes ||
+      !dymax || !dxmax || !(keep > 0.f) || (dxsum && !dxsum_part) || (dxsum2 && !dxsum) ||
+      (size_t)B * HW * C * 4 >= 0x80000000ull)
     return (int)hipErrorInvalidValue;
-  const int cpg = C / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0) return (int)hipErrorInvalidValue;
-  GnBwdArgs a{dy, x, nullptr, C, 0, gamma, beta, mean, rstd, nullptr, nullptr, dgamma_part, dbeta_part,
-              B, G, act, keep, seed, offset, 0, dxmax, nullptr, nullptr, nullptr, dxsum_part, seed_dev, tickets, dgamma,
-              dbeta, dxsum, dxsum2, static_cast<unsigned char*>(dxplanes), dymax, keep < 1.f ? keepbits : nullptr};
-  hipLaunchKernelGGL(gn_bwd_kernel_1pass, dim3(B, C / 32), dim3(512), 0, stream, a);
-  MULAN_CHECK_LAUNCH();
+  const GnBwdArgs a{.dy = dy, .x1 = x, .C1 = C, .gamma = gamma, .beta = beta, .mean = mean, .rstd = rstd,
+                    .dgamma_part = dgamma_part, .dbeta_part = dbeta_part, .B = B, .G = G, .act = act, .keep = keep,
+                    .seed = seed, .offset = offset, .dx1max = dxmax, .dxsum_part = dxsum_part, .seed_dev = seed_dev,
+                    .tickets = tickets, .dgamma = dgamma, .dbeta = dbeta, .dxsum = dxsum, .dxsum2 = dxsum2,
+                    .dx1planes = static_cast<unsigned char*>(dxplanes), .dymax = dymax,
+                    .maskbits = keep < 1.f ? keepbits : nullptr};
+  return launch_gn_bwd(a, stream);
 }
 
 MULAN_API int mulan_groupnorm_bwd(const float* dy, const float* x1, const float* x2, int C1, int C2,
@@ -1121,16 +1127,16 @@ MULAN_API int mulan_groupnorm_fwd_stream(const float* x1, const float* x2, int C
                                          unsigned long long offset,
                                          const unsigned long long* seed_dev, unsigned* ymax, unsigned* keepbits,
                                          hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0 || !mean || !rstd || (!y == !yplanes) || !(keep > 0.f) ||
+  if (!gn_shape_ok(C1, C2, B, hw, G, ymax != nullptr) || !mean || !rstd || (!y == !yplanes) || !(keep > 0.f) ||
       (yplanes && !ymax) || (xstats1 && C2 > 0 && !xstats2) || (keepbits && !(keep < 1.f)) ||
       (xstats1 && xstats_tiles != 4 && xstats_tiles != 8 && xstats_tiles != 16))
     return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0 || C1 % cpg != 0 || (ymax && Ct / 32 > 16))
-    return (int)hipErrorInvalidValue;
-  GnArgs a{x1, x2, C1, C2, gamma, beta, y, mean, rstd, B, G, eps, act, keep, seed, offset, ymax, seed_dev,
-           static_cast<unsigned char*>(yplanes), keepbits, 0, xstats1, xstats2, xstats_tiles};
+  const int Ct = C1 + C2;
+  if (C1 % (Ct / G) != 0) return (int)hipErrorInvalidValue;
+  const GnArgs a{.x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .y = y, .mean = mean, .rstd = rstd,
+                 .B = B, .G = G, .eps = eps, .act = act, .keep = keep, .seed = seed, .offset = offset, .ymax = ymax,
+                 .seed_dev = seed_dev, .yplanes = static_cast<unsigned char*>(yplanes), .maskbits = keepbits,
+                 .xstats1 = xstats1, .xstats2 = xstats2, .xstats_tiles = xstats_tiles};
   // tune[20] (dev A/B): quarters of a slab per block -- 0 / 4: 1024 threads, 2: 512, 1: 256 (the maxima array has 16
   // entries per image: (slabs) x (z blocks) must fit -- in planes mode too, where every part receives the bound: with
   // tune[20] = 1 and 256 channels the parts 16 .. 31 of the last image lay behind the end of the array)
@@ -1156,17 +1162,18 @@ MULAN_API int mulan_groupnorm_bwd_stream(const float* dy, const unsigned* dymax,
                                          const float* add1, const float* add2, const float* add1b, float* dxsum_part,
                                          float* dgamma, float* dbeta, float* dxsum, float* dxsum2, unsigned* tickets,
                                          const unsigned* keepbits, hipStream_t stream) {
-  const int Ct = C1 + C2;
-  if (hw != HW || B <= 0 || G <= 0 || Ct % G != 0 || !gstats || !tickets || !dgamma || !dbeta || !dgamma_part ||
-      !dbeta_part || (dxsum && !dxsum_part) || (dxsum2 && !dxsum) || Ct / 32 > 16 || !(keep > 0.f) ||
-      (!dx1 == !dx1planes) || (C2 > 0 && !dx2) ||
+  if (!gn_shape_ok(C1, C2, B, hw, G, true) || !gstats || !tickets || !dgamma || !dbeta || !dgamma_part || !dbeta_part ||
+      (dxsum && !dxsum_part) || (dxsum2 && !dxsum) || !(keep > 0.f) || (!dx1 == !dx1planes) || (C2 > 0 && !dx2) ||
       (dx1planes && (C2 != 0 || add1 || add1b || !dymax || !dx1max || (size_t)B * HW * C1 * 4 >= 0x80000000ull)))
     return (int)hipErrorInvalidValue;
-  const int cpg = Ct / G;
-  if (cpg % 4 != 0 || 32 % cpg != 0 || C1 % 32 != 0 || C2 % 32 != 0) return (int)hipErrorInvalidValue;
-  GnBwdArgs a{dy, x1, x2, C1, C2, gamma, beta, mean, rstd, dx1, dx2, dgamma_part, dbeta_part,
-              B, G, act, keep, seed, offset, 0, dx1max, dx2max, add1, add2, dxsum_part, seed_dev, tickets, dgamma, dbeta,
-              dxsum, dxsum2, static_cast<unsigned char*>(dx1planes), dymax, keep < 1.f ? keepbits : nullptr, add1b, gstats};
+  const int Ct = C1 + C2;
+  const GnBwdArgs a{.dy = dy, .x1 = x1, .x2 = x2, .C1 = C1, .C2 = C2, .gamma = gamma, .beta = beta, .mean = mean,
+                    .rstd = rstd, .dx1 = dx1, .dx2 = dx2, .dgamma_part = dgamma_part, .dbeta_part = dbeta_part, .B = B, .G = G,
+                    .act = act, .keep = keep, .seed = seed, .offset = offset, .dx1max = dx1max, .dx2max = dx2max,
+                    .add1 = add1, .add2 = add2, .dxsum_part = dxsum_part, .seed_dev = seed_dev, .tickets = tickets,
+                    .dgamma = dgamma, .dbeta = dbeta, .dxsum = dxsum, .dxsum2 = dxsum2,
+                    .dx1planes = static_cast<unsigned char*>(dx1planes), .dymax = dymax,
+                    .maskbits = keep < 1.f ? keepbits : nullptr, .add1b = add1b, .gstats = gstats};
   // tune[21] (dev A/B): quarters of a slab per block (as tune[20]); tune[22] = 1 / 2: load batches of 4 / 2 pixels instead of 8.
   // The per-block partial rows are [B * 4 / nsp][Ct]: dgamma_part / dbeta_part / dxsum_part must hold 4 B rows.
   int nsp = g_mulan_tune[21] == 1 ? 1 : (g_mulan_tune[21] == 2 ? 2 : 4);

@@ -14,6 +14,7 @@ Ill-conditioned data (test_cancellation): never fixed in advance -- see its docs
 
 Figures the tests print (MI355X, this commit) are recorded in the docstrings of the tests that print them.
 """
+import copy
 import functools
 
 import numpy as np
@@ -295,7 +296,7 @@ def written(t):
 
 
 # ------------------------------------------------------------------------------------------------ launch helpers
-def run_fwd(ops, c, name, *, planes=False, ymax=True, keepbits=False, xstats=0, given=False, seed_dev=True):
+def run_fwd(ops, c, name, *, planes=False, ymax=True, keepbits=False, xstats=0, given=False, seed_dev=True, hw=HW):
     """one forward entry point on case c with poisoned outputs -> dict of what it wrote"""
     p, B, Ct = ops.ptr, c.B, c.Ct
     o = {"mean": new(B, c.G), "rstd": new(B, c.G)}
@@ -305,7 +306,7 @@ def run_fwd(ops, c, name, *, planes=False, ymax=True, keepbits=False, xstats=0, 
     o["kb"] = new(B * (Ct // 32) * 1024, dtype=torch.int32) if keepbits else None
     sd = c.seed_dev if seed_dev else None
     head = (p(c.x1), p(c.x2), c.C1, c.C2, p(c.gamma), p(c.beta))
-    tail = (B, HW, c.G, EPS, c.act, c.keep, SEED, OFFSET)
+    tail = (B, hw, c.G, EPS, c.act, c.keep, SEED, OFFSET)
     if name == "mulan_groupnorm_fwd":
         args = head + (p(o["y"]), p(o["mean"]), p(o["rstd"])) + tail + (p(o["ymax"]), ops.stream())
     elif name == "mulan_groupnorm_fwd_dyn":
@@ -315,7 +316,7 @@ def run_fwd(ops, c, name, *, planes=False, ymax=True, keepbits=False, xstats=0, 
     elif name == "mulan_groupnorm_fwd_planes_keepbits":
         args = head + (p(o["planes"]), p(o["mean"]), p(o["rstd"])) + tail + (p(sd), p(o["ymax"]), p(o["kb"]), ops.stream())
     elif name == "mulan_groupnorm_stats":
-        args = head + (p(o["mean"]), p(o["rstd"]), p(o["ymax"]), B, HW, c.G, EPS, ops.stream())
+        args = head + (p(o["mean"]), p(o["rstd"]), p(o["ymax"]), B, hw, c.G, EPS, ops.stream())
     else:
         assert name == "mulan_groupnorm_fwd_stream"
         xs1, xs2 = c.xstats(xstats) if xstats else (None, None)
@@ -329,8 +330,9 @@ def run_fwd(ops, c, name, *, planes=False, ymax=True, keepbits=False, xstats=0, 
 
 
 def run_bwd(ops, c, name, *, planes=False, maxima=True, adds=(), accumulate=False, kb=None, sums=True, seed_dev=True,
-            bufs=None):
-    """one backward entry point on case c (mean / rstd: the float64 ones rounded to fp32) with poisoned outputs"""
+            bufs=None, hw=HW, null=()):
+    """one backward entry point on case c (mean / rstd: the float64 ones rounded to fp32) with poisoned outputs; null:
+    buffers ("tick", "dymax") handed over as NULL"""
     p, B, Ct, C1, C2 = ops.ptr, c.B, c.Ct, c.C1, c.C2
     rows = 4 * B if name == "mulan_groupnorm_bwd_stream" else B          # the streaming form leaves up to 4 rows per image
     o = bufs or {}
@@ -354,10 +356,12 @@ def run_bwd(ops, c, name, *, planes=False, maxima=True, adds=(), accumulate=Fals
     a2 = c.add2 if "add2" in adds else None
     a1b = c.add1b if "add1b" in adds else None
     sd = c.seed_dev if seed_dev else None
-    dymax = ops.absmax_rows(c.dy.view(B, -1)) if planes else None
+    dymax = ops.absmax_rows(c.dy.view(B, -1)) if planes and "dymax" not in null else None
+    if "tick" in null:
+        o["tick"] = None
     o["dymax"] = dymax
     stats = (p(c.gamma), p(c.beta), p(c.mean32), p(c.rstd32))
-    mid = (B, HW, c.G, c.act, c.keep, SEED, OFFSET)
+    mid = (B, hw, c.G, c.act, c.keep, SEED, OFFSET)
     tot = (p(o["dxsp"]), p(o["dg"]), p(o["db"]), p(o["dxs"]), p(o["dxs2"]), p(o["tick"]))
     if name in ("mulan_groupnorm_bwd", "mulan_groupnorm_bwd_dyn"):
         args = (p(c.dy), p(c.x1), p(c.x2), C1, C2) + stats + (p(o["dx1"]), p(o["dx2"]), p(o["dgp"]), p(o["dbp"])) + mid + \
@@ -889,6 +893,84 @@ def test_images_past_two_gigabytes(ops):
         check_each("2 GB " + name + " dxsum_part", dxsp[pick], ref_dx.sum(1))
         check_maxima("2 GB " + name + " dxmax", mx[pick].contiguous(), dx[pick], 16)
         del dx
+
+
+# ------------------------------------------------------------------------------------------------ H: refusals
+# label -> (entry point, the launch helper's keywords); the streaming forms twice each: fp32 output (forward: mean / rstd
+# given), and planes (forward: + stored keep-bits)
+ENTRIES = {
+    "fwd": ("mulan_groupnorm_fwd", dict(seed_dev=False)),
+    "fwd_dyn": ("mulan_groupnorm_fwd_dyn", {}),
+    "fwd_planes": ("mulan_groupnorm_fwd_planes", dict(planes=True)),
+    "fwd_planes_keepbits": ("mulan_groupnorm_fwd_planes_keepbits", dict(planes=True, keepbits=True)),
+    "stats": ("mulan_groupnorm_stats", {}),
+    "fwd_stream": ("mulan_groupnorm_fwd_stream", dict(given=True)),
+    "fwd_stream[planes,keepbits]": ("mulan_groupnorm_fwd_stream", dict(given=True, planes=True, keepbits=True)),
+    "bwd": ("mulan_groupnorm_bwd", dict(seed_dev=False)),
+    "bwd_dyn": ("mulan_groupnorm_bwd_dyn", {}),
+    "bwd_fused": ("mulan_groupnorm_bwd_fused", {}),
+    "bwd_fused_planes": ("mulan_groupnorm_bwd_fused_planes", dict(planes=True)),
+    "bwd_stream": ("mulan_groupnorm_bwd_stream", {}),
+    "bwd_stream[planes]": ("mulan_groupnorm_bwd_stream", dict(planes=True)),
+}
+# One row per argument set: what it changes on the valid call (B = 1, 64 channels, 16 groups, keep 0.9; "case": fields of
+# the case, "fwd" / "bwd": keywords of run_fwd / run_bwd) and, per entry point in the order of ENTRIES, A = accepted
+# (returns 0 and writes), R = refused (hipErrorInvalidValue, every output still poison), - = the entry point has no such
+# argument.  Read off the entry points' conditions in groupnorm.hip as they stood before they shared gn_shape_ok:
+#   every one:  hw == 1024, B > 0, G > 0, G | Ct, cpg in {4, 8, 16, 32}, 32 | C1, 32 | C2
+#   keep:       _fwd / _fwd_dyn / _bwd / _bwd_dyn / _bwd_fused take any; _fwd_planes, _fwd_stream, _bwd_fused_planes and
+#               _bwd_stream keep > 0; _fwd_planes_keepbits 0 < keep < 1; _fwd_stream with keepbits keep < 1
+#   pointers:   ymax / bound required by _fwd_planes, _fwd_planes_keepbits, _stats and _fwd_stream with planes, the
+#               maxima and dymax by _bwd_fused_planes and _bwd_stream with planes, tickets by the fused and the
+#               streaming backward; the maxima are optional everywhere else
+REFUSALS = {
+    #                                                                                  forward  backward
+    "valid":        (dict(),                                                           "AAAAAAA" "AAAAAA"),
+    "hw=512":       (dict(fwd=dict(hw=512), bwd=dict(hw=512)),                         "RRRRRRR" "RRRRRR"),
+    "G=5":          (dict(case=dict(G=5)),                                             "RRRRRRR" "RRRRRR"),   # 5 does not divide 64
+    "cpg=2":        (dict(case=dict(G=32)),                                            "RRRRRRR" "RRRRRR"),
+    "C1=48":        (dict(case=dict(C1=48, C2=48, Ct=96, G=12)),                       "RRRRRRR" "RRRRRR"),   # (whole groups: 96 / 12, and 48 / 12 alone)
+    "keep=0":       (dict(case=dict(keep=0.0)),                                        "AARR-RR" "AAARRR"),
+    "keep=1":       (dict(case=dict(keep=1.0)),                                        "AAAR-AR" "AAAAAA"),
+    "no maxima":    (dict(fwd=dict(ymax=False), bwd=dict(maxima=False)),               "AARRRAR" "AAARAR"),
+    "no tickets":   (dict(bwd=dict(null=("tick",))),                                   "-------" "--RRRR"),
+    "no dymax":     (dict(bwd=dict(null=("dymax",))),                                  "-------" "---R-R"),
+}
+REFUSAL_CELLS = [pytest.param(label, row, want[i], id=f"{label}-{row}")
+                 for row, (_, want) in REFUSALS.items() for i, label in enumerate(ENTRIES) if want[i] != "-"]
+
+
+@pytest.mark.parametrize("label,row,want", REFUSAL_CELLS)
+def test_refusals_are_per_entry_point(ops, label, row, want):
+    """H: the argument checks, entry point by entry point (REFUSALS above).  The shape conditions are common to the family;
+    the keep ranges, the required pointers and the caps are each entry point's own: keep = 1 is accepted by _fwd_planes and
+    refused by _fwd_planes_keepbits, keep = 0 is accepted by _bwd_fused and refused by _bwd_fused_planes, a missing maxima
+    array is accepted by _fwd_dyn and refused by _stats.  A refused call leaves every output at its poison value (and the
+    tickets at zero).  (More than 16 slabs: test_forward_grid / test_backward_grid.)
+    An accepted row is held to return code 0 and to a main output that is no longer poison, not to its values (those are
+    the other tests'): with keep = 0 the accepting kernels scale by 1 / keep and mask everything out."""
+    name, kw = ENTRIES[label]
+    change = REFUSALS[row][0]
+    # a shallow copy of the cached case with the row's fields overwritten: its tensors and derived fields (x1, mean32, ...)
+    # keep the valid shape.  The rows that change a shape (G, C1 / C2 / Ct) are refused everywhere, before any launch, so
+    # nothing reads them; the rows that launch change only keep, which no buffer size depends on
+    c = copy.copy(case(1, 64, 0, 16, 1, 0.9))
+    for k, v in change.get("case", {}).items():
+        setattr(c, k, v)
+    fwd = "fwd" in name or name.endswith("stats")
+    o = (run_fwd if fwd else run_bwd)(ops, c, name, **{**kw, **change.get("fwd" if fwd else "bwd", {})})
+    outs = ("y", "planes", "ymax", "kb") + (() if kw.get("given") else ("mean", "rstd")) if fwd else \
+        ("dx1", "dx2", "planes", "dgp", "dbp", "dxsp", "mx1", "mx2", "dg", "db", "dxs", "dxs2")
+    poison = {torch.float32: POISON_F, torch.int32: POISON_I, torch.uint8: 0xA5}
+    untouched = {k: bool((o[k] == poison[o[k].dtype]).all()) for k in outs if o[k] is not None}
+    if want == "R":
+        assert o["rc"] == INVALID, (label, row, o["rc"])
+        assert all(untouched.values()), (label, row, untouched)
+        assert o.get("tick") is None or int(o["tick"].abs().sum()) == 0
+    else:
+        assert o["rc"] == 0, (label, row, o["rc"])
+        main = "mean" if name.endswith("stats") else ("planes" if kw.get("planes") else ("y" if fwd else "dx1"))
+        assert not untouched[main], (label, row, untouched)
 
 
 # ------------------------------------------------------------------------------------------------ autograd wiring
