@@ -599,6 +599,24 @@ int mulan_diffloss_bwd(int mode, const unsigned char* x, const float* gt, const 
                        int per_element_gamma, const float* eps, const float* zt, const float* net,
                        const float* dloss, float* dnet, float* dgt, float* dgprime, float* dzt, int B, int d,
                        mulan_stream_t stream);
+/* The variational bound of B rows taken apart: the per-element terms of mulan_qsample_fwd (the reconstruction term rho_i
+ * and the prior KL kappa_i) and of mulan_diffloss_fwd (d_i, for the same `mode`, with w where that takes gprime: gamma'(t)
+ * or T expm1(gamma_t - gamma_s)), reduced over each row and over each group of rows_per_group consecutive rows
+ * (B = G rows_per_group) without being written per element.  Each output may be NULL, not both:
+ *   rows_out [B][8]     sum d, the sums of d over the three channels (sub-pixel i is channel i % 3), sum rho, sum kappa,
+ *                       the sum of the squared residual r_i^2 (r = eps - eps_hat in mode 2, v* - v_hat in modes 0, 1), the
+ *                       mean of the factor of r_i^2 / 2 in d_i (w in mode 2, (1 - sigmoid(gt)) w in modes 0, 1)
+ *   cols_out [G][3][d]  per group, the mean over its rows of d_i, rho_i, kappa_i
+ * workspace: mulan_bound_profile_workspace(B, rows_per_group) bytes, needed with cols_out.  Every sum is taken in one
+ * fixed order (no floating-point atomics): the same bits on every run and device.  zt is read in mode 1 only.  The
+ * fp32 [B][d] arrays, cols_out and workspace must be 16-byte aligned, x 4-byte.
+ * hipErrorInvalidValue, before anything is launched, for d != 3072, B <= 0, rows_per_group <= 0, B not a multiple of
+ * rows_per_group, mode outside 0..2, a NULL input, both outputs NULL, cols_out without workspace, a misaligned pointer. */
+size_t mulan_bound_profile_workspace(int B, int rows_per_group);
+int mulan_bound_profile(int mode, const unsigned char* x, const float* g0, const float* g1, const float* gt,
+                        const float* w, int per_element_gamma, const float* eps0, const float* eps, const float* zt,
+                        const float* net, float* rows_out, float* cols_out, float* workspace, int B, int d,
+                        int rows_per_group, mulan_stream_t stream);
 /* _topk_embedding_and_loss + _gamma_noise + _gumbel_kl_loss (model_mulan_velocity.py:78-120).
  * gnoise: [10,B,L] raw Gamma(1/k,1) draws; tau < 0: gnoise is [B,L] additive noise (topk_noise_type 'gumbel',
  * model_mulan_epsilon.py:236-239); gnoise = NULL: hard k-hot of the plain logits (soft / nrm may be NULL). */

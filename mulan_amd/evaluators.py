@@ -709,3 +709,89 @@ def plot_histogram(hist, count=3, cols=5):
             plt.yticks([])
         figs.append(fig)
     return figs
+
+
+# ------------------------------------------------------------------ the bound taken apart (not in the reference)
+BITS = 1.0 / float(np.log(2.0))
+
+
+def bound_profile(experiment, images, n_timesteps=128, eval_step0=0):
+    """Where the bits of the dense evaluator's bound come from: each uint8 image of `images` [N, 32, 32, 3] is tiled
+    n_timesteps = T times under PRNGKey(0) with same_image=True inside _packed_weights, exactly as _dense_partial scores
+    it (image n at step eval_step0 + n, labels 0), and the pass's loss heads are reduced per row and per sub-pixel on the
+    device (ops.bound_profile through the models' profile_rows).  A dict of numpy arrays, in bits per dimension (divided
+    by 3072 ln 2) unless stated:
+      t [N, T] the antithetic times of the rows;  diff [N, T] the diffusion integrand, diff_channel [N, T, 3] its three
+      channel parts;  recon, klz [N, T] the reconstruction and prior-KL terms;  kl_z [N] the latent KL;  resid2, weight
+      [N, T] the raw sum of squared residuals and mean loss weight of each row;  diff_pixel, recon_pixel, klz_pixel
+      [N, 3072] the row means per sub-pixel, in bits (diff_pixel.sum(1) / 3072 == diff.mean(1));  bpd [N] = recon + klz +
+      kl_z + diff as row means, what loss_fn returns for the image;  diff_std [N] the population standard deviation of
+      diff over the rows.
+    model_vdm.VDM (no per-pixel schedule) is accepted: the baseline to compare with.  One rank only."""
+    if getattr(experiment, "world", 1) > 1:
+        raise ValueError(f"bound_profile runs on one rank, this experiment has world = {experiment.world}: evaluate a "
+                         "slice of the images per process instead")
+    images = torch.as_tensor(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or tuple(images.shape[1:]) != (32, 32, 3) or images.shape[0] < 1:
+        raise ValueError(f"images are uint8 [N, 32, 32, 3] with N >= 1, got {images.dtype} {list(images.shape)}")
+    T = int(n_timesteps)
+    if T < 1:
+        raise ValueError(f"n_timesteps must be >= 1, got {n_timesteps}")
+    dev = experiment.device
+    _, sample_rng = PRNGKey(0).split()                    # loss_fn's split of the evaluators' key
+    same = {'same_image': True} if hasattr(experiment.model, "parameterization") else {}
+    labels = torch.zeros(T, dtype=torch.int32, device=dev)
+    conditioning = torch.zeros(T, dtype=torch.uint8, device=dev)
+    per_image = []
+    with _packed_weights(experiment):
+        for n in range(images.shape[0]):
+            tiled = images[n:n + 1].to(dev).expand(T, 32, 32, 3).contiguous()
+            with torch.no_grad():
+                _, prof = experiment.state.apply_fn(experiment.orig_params, tiled, labels, conditioning,
+                                                    step=eval_step0 + n, rngs={'sample': sample_rng}, deterministic=True,
+                                                    profile_rows=T, **same)
+            per_image.append({k: prof[k].detach().double().cpu().numpy() for k in ("rows", "cols", "kl_z", "t")})
+    return _profile_arrays(per_image)
+
+
+def _profile_arrays(per_image):
+    """the host arithmetic of bound_profile: per image rows [T, 8], cols [1, 3, 3072], kl_z [T], t [T] as float64"""
+    per_dim = BITS / 3072.0
+    rows = np.stack([p["rows"] for p in per_image])                          # [N, T, 8]
+    cols = np.stack([p["cols"][0] for p in per_image])                       # [N, 3, 3072]
+    out = dict(t=np.stack([p["t"] for p in per_image]).astype(np.float32),
+               diff=rows[..., 0] * per_dim, diff_channel=rows[..., 1:4] * per_dim, recon=rows[..., 4] * per_dim,
+               klz=rows[..., 5] * per_dim, kl_z=np.stack([p["kl_z"].mean() for p in per_image]) * per_dim,
+               resid2=rows[..., 6], weight=rows[..., 7],
+               diff_pixel=cols[:, 0] * BITS, recon_pixel=cols[:, 1] * BITS, klz_pixel=cols[:, 2] * BITS)
+    out["bpd"] = out["recon"].mean(1) + out["klz"].mean(1) + out["kl_z"] + out["diff"].mean(1)
+    out["diff_std"] = out["diff"].std(1)
+    return out
+
+
+def plot_bound_profile(profile, count=3):
+    """for the first `count` images of a bound_profile: the diffusion integrand over t (the whole and its three
+    channels) and the 32 x 32 maps of diff_pixel per channel"""
+    import matplotlib.pyplot as plt
+    figs = []
+    for n in range(min(count, len(profile["bpd"]))):
+        order = np.argsort(profile["t"][n])
+        t = profile["t"][n][order]
+        fig = plt.figure(figsize=(12, 3))
+        ax = fig.add_subplot(1, 4, 1)
+        ax.plot(t, profile["diff"][n][order], color='k', label='all')
+        for ch, colour in enumerate(('r', 'g', 'b')):
+            ax.plot(t, profile["diff_channel"][n][order, ch], color=colour, label=f'channel {ch}')
+        ax.set_xlabel('$t$')
+        ax.set_ylabel('bits / dim')
+        ax.set_title(f"bpd {profile['bpd'][n]:.3f}  std {profile['diff_std'][n]:.3f}", fontsize=8)
+        ax.legend(fontsize=6)
+        maps = np.asarray(profile["diff_pixel"][n]).reshape(32, 32, 3)
+        for ch in range(3):
+            ax = fig.add_subplot(1, 4, 2 + ch)
+            ax.imshow(maps[..., ch], cmap='hot', interpolation='nearest', vmin=0.0, vmax=float(maps.max()))
+            ax.set_title(f'diffusion bits, channel {ch}', fontsize=8)
+            ax.set_xticks([])
+            ax.set_yticks([])
+        figs.append(fig)
+    return figs

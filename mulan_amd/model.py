@@ -905,11 +905,14 @@ class MulanVDM(_VDMBase):
         return {"score_model": score, "encoder_model": enc, "gamma": gamma}
 
     def apply(self, params, images, labels=None, conditioning=None, step=0, rngs=None, deterministic=True,
-              noise=None, return_aux=False, same_image=False):
+              noise=None, return_aux=False, same_image=False, profile_rows=0):
         """same_image (not in the reference): the caller vouches that every row of `images` is the same image (the dense
         variational-bound evaluator tiles one test image n_timesteps times, ldm/notebook_utils.py:181-186).  The encoder
         U-Net sees neither t nor the noise, so in evaluation mode its logits are identical for all rows: it then runs on
-        one row and the logits are broadcast (7 % of the evaluator's FLOPs; same bits)."""
+        one row and the logits are broadcast (7 % of the evaluator's FLOPs; same bits).
+        profile_rows = R > 0 (not in the reference; B a multiple of R): returns (output, profile) instead, the profile
+        of this very pass -- its noise, times and network output -- as a dict: rows [B, 8] and cols [B / R, 3, 3072] of
+        ops.bound_profile, the latent KL kl_z [B] (which loss_klz includes) and the times t [B]."""
         cfg = self.config
         dev = images.device
         x = images.reshape(-1, D).contiguous()
@@ -959,17 +962,19 @@ class MulanVDM(_VDMBase):
         net = score_unet(params["score_model"], cfg, zt.view(B, HW, 3), g_in, cond, _Drop(k_score, cfg.sm_pdrop))
         net = net.reshape(B, D)
         T = cfg.sm_n_timesteps
+        mode, w = 2, gp
         if self.parameterization == "velocity":
             mode = 1 if cfg.velocity_from_epsilon else 0
-            loss_diff = ops.diffusion_loss(mode, x, gt, gp, noise["eps"], zt, net)
-        elif T == 0:
-            loss_diff = ops.diffusion_loss(2, x, gt, gp, noise["eps"], zt, net)
-        else:
+        elif T > 0:
             # finite depth T (ldm/model_mulan_epsilon.py:348-355): s = t - 1/T, weight T * expm1(g_t - g_s)
             _, _, gs, _ = ops.poly_gamma(a, b, c, t - 1.0 / T, cfg.gamma_min, cfg.gamma_max)
-            loss_diff = ops.diffusion_loss(2, x, gt, ops.expm1_weight(gt, gs, T), noise["eps"], zt, net)
+            w = ops.expm1_weight(gt, gs, T)
+        loss_diff = ops.diffusion_loss(mode, x, gt, w, noise["eps"], zt, net)
         out = VDMOutput(loss_recon=loss_recon, loss_klz=kl_z + loss_klz, loss_diff=loss_diff, var_0=v0.mean(),
                         var_1=v1.mean())
+        if profile_rows:
+            rows, cols = ops.bound_profile(mode, x, g0, g1, gt, w, noise["eps_0"], noise["eps"], zt, net, profile_rows)
+            return out, dict(rows=rows, cols=cols, kl_z=kl_z, t=t)
         if return_aux:
             return out, dict(emb=emb, zt=zt, net=net, gt=gt, gp=gp, t=t, logits=logits if cfg.reparam_type == 'true' else None)
         return out
@@ -1175,7 +1180,8 @@ class PlainVDM(_VDMBase):
         return b + aw * t, aw.expand_as(t)
 
     def apply(self, params, images, labels=None, conditioning=None, step=0, rngs=None, deterministic=True,
-              noise=None, return_aux=False):
+              noise=None, return_aux=False, profile_rows=0):
+        """profile_rows: as MulanVDM.apply takes it (per-row gammas; kl_z is zero: there is no latent)"""
         cfg = self.config
         dev = images.device
         x = images.reshape(-1, D).contiguous()
@@ -1203,6 +1209,10 @@ class PlainVDM(_VDMBase):
         net = score_unet(params["score_model"], cfg, zt.view(B, HW, 3), gt, cond, _Drop(drop_key, cfg.sm_pdrop))
         loss_diff = ops.diffusion_loss(2, x, gt.contiguous(), gp.contiguous(), noise["eps"], zt, net.reshape(B, D))
         out = VDMOutput(loss_recon=loss_recon, loss_klz=loss_klz, loss_diff=loss_diff, var_0=v0.mean(), var_1=v1.mean())
+        if profile_rows:
+            rows, cols = ops.bound_profile(2, x, g0.contiguous(), g1.contiguous(), gt.contiguous(), gp.contiguous(),
+                                           noise["eps_0"], noise["eps"], zt, net.reshape(B, D), profile_rows)
+            return out, dict(rows=rows, cols=cols, kl_z=torch.zeros(B, device=dev), t=t)
         if return_aux:
             return out, dict(zt=zt, net=net, gt=gt, gp=gp, t=t)
         return out

@@ -2324,6 +2324,50 @@ def schedule_curves(a, b, c, t, gmin, gmax, *, curves=True, stats=False, bins=No
     return gamma, st, hist
 
 
+def bound_profile(mode, x, g0, g1, gt, w, eps0, eps, zt, net, rows_per_group, rows=True, cols=True):
+    """(rows | None, cols | None): the loss heads of B rows kept per element long enough to be reduced both ways, one
+    entry point (mulan_bound_profile).  mode, x (uint8 [B, 3072]), gt, w, eps, zt, net as diffusion_loss takes them (w its
+    `gp`: gamma'(t), or expm1_weight), g0, g1, eps0 as qsample takes them; the four gammas fp32 [B, 3072], or all [B]
+    (the scalar schedule).  Rows g R .. g R + R - 1 form group g, R = rows_per_group.
+    rows: fp32 [B, 8] -- the sum of the diffusion term d, its three channel sums (sub-pixel i is channel i % 3), the sums
+    of the reconstruction and the prior-KL term, the sum of the squared residual, the mean of the factor of r^2 / 2 in d.
+    cols: fp32 [G, 3, 3072] -- per group, the row means of d, the reconstruction and the prior-KL term per sub-pixel."""
+    if mode not in (0, 1, 2):
+        raise ValueError(f"bound_profile: mode is 0 (velocity), 1 (velocity from epsilon) or 2 (epsilon), got {mode!r}")
+    if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1:
+        raise ValueError(f"bound_profile: x is uint8 [B, {D}]; got "
+                         f"{(x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__}")
+    B = x.shape[0]
+    wide = {"eps0": eps0, "eps": eps, "zt": zt, "net": net}
+    gammas = {"g0": g0, "g1": g1, "gt": gt, "w": w}
+    for name, v in {**wide, **gammas}.items():
+        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.device != x.device:
+            raise ValueError(f"bound_profile: {name} is an fp32 tensor on {x.device}; got "
+                             f"{(v.dtype, v.device) if torch.is_tensor(v) else type(v).__name__}")
+    for name, v in wide.items():
+        if tuple(v.shape) != (B, D):
+            raise ValueError(f"bound_profile: {name} is fp32 [{B}, {D}]; got {tuple(v.shape)}")
+    per_elem = tuple(gt.shape) == (B, D)
+    for name, v in gammas.items():
+        if tuple(v.shape) != ((B, D) if per_elem else (B,)):
+            raise ValueError(f"bound_profile: g0, g1, gt, w are all [{B}, {D}] or all [{B}]; {name} is {tuple(v.shape)}")
+    R = int(rows_per_group)
+    if R < 1 or B % R:
+        raise ValueError(f"bound_profile: {B} rows are no whole number of groups of rows_per_group = {rows_per_group}")
+    if not (rows or cols):
+        raise ValueError("bound_profile: nothing asked for (rows and cols are both off)")
+    x, g0, g1, gt, w, eps0, eps, zt, net = (_c(v) for v in (x, g0, g1, gt, w, eps0, eps, zt, net))
+    dev = x.device
+    rows_out = torch.empty((B, 8), device=dev, dtype=torch.float32) if rows else None
+    cols_out = ws = None
+    if cols:
+        cols_out = torch.empty((B // R, 3, D), device=dev, dtype=torch.float32)
+        ws = torch.empty(lib.load().mulan_bound_profile_workspace(B, R) // 4, device=dev, dtype=torch.float32)
+    call("mulan_bound_profile", int(mode), ptr(x), ptr(g0), ptr(g1), ptr(gt), ptr(w), int(per_elem), ptr(eps0), ptr(eps),
+         ptr(zt), ptr(net), ptr(rows_out), ptr(cols_out), ptr(ws), B, D, R, stream())
+    return rows_out, cols_out
+
+
 # ----------------------------------------------------------------------------- exact-likelihood ODE (eval only)
 def topk_hard(logits, k):
     """(k-hot embedding of the plain logits, KL(softmax(logits) || uniform)): notebook_utils.logits_to_embeddings and
