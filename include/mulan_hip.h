@@ -617,6 +617,29 @@ int mulan_bound_profile(int mode, const unsigned char* x, const float* g0, const
                         const float* w, int per_element_gamma, const float* eps0, const float* eps, const float* zt,
                         const float* net, float* rows_out, float* cols_out, float* workspace, int B, int d,
                         int rows_per_group, mulan_stream_t stream);
+/* Exact k nearest neighbours between uint8 rows, on the int8 matrix cores (neighbours.hip): for every row i of q [Q][D] the
+ * k smallest squared Euclidean distances d2(i, j) = sum_c (q[i][c] - r[j][c])^2 to the rows j of r [N][D], as integers.
+ *   dist2 [Q][k]  ascending; idx [Q][k] the reference's global index j + idx_base.  Equal distances go to the smaller
+ *                 global index, so the result is a function of the inputs alone (not of splits, the device or the
+ *                 schedule; no atomics).  Slots beyond the qualifying references hold dist2 = INT32_MAX, idx = -1.
+ *   self_offset   >= 0: the pair with j + idx_base == i + self_offset does not qualify (a set against itself); -1: none.
+ *   accumulate    1: dist2 / idx are in/out, and this call's candidates are merged into the lists already there (which
+ *                 are sorted and hold global indices of other calls, or the empty slot): a reference set walked in
+ *                 chunks gives what one call over the whole set gives.  0: they are outputs.
+ *   splits        0: the library cuts the reference range into slices; > 0: that many (at most 4096; slices beyond the
+ *                 128-row reference tiles are empty).  The answer does not depend on it.
+ *   radius2 [N], covered [Q]   both or neither.  covered[i] = 1 if some qualifying j has d2(i, j) <= radius2[j], else 0;
+ *                 with accumulate the new value is OR-ed into the old one.
+ *   workspace     mulan_knn_u8_workspace(Q, k, splits) bytes (0 for arguments that are refused), 8-byte aligned.
+ * q and r must be 16-byte aligned, the int arrays 4-byte.
+ * hipErrorInvalidValue, before anything is launched, for D not a multiple of 64 in [64, 16384], k outside 1..16,
+ * Q < 1, N < 1, idx_base < 0 or idx_base + N > INT32_MAX, self_offset < -1, accumulate outside 0..1, splits outside
+ * 0..4096, a NULL q / r / dist2 / idx / workspace, radius2 without covered or covered without radius2, a misaligned
+ * pointer. */
+size_t mulan_knn_u8_workspace(int Q, int k, int splits);
+int mulan_knn_u8(const unsigned char* q, const unsigned char* r, int Q, int N, int D, int k, int idx_base,
+                 int self_offset, int accumulate, int splits, const int* radius2, unsigned char* covered, int* dist2,
+                 int* idx, void* workspace, mulan_stream_t stream);
 /* _topk_embedding_and_loss + _gamma_noise + _gumbel_kl_loss (model_mulan_velocity.py:78-120).
  * gnoise: [10,B,L] raw Gamma(1/k,1) draws; tau < 0: gnoise is [B,L] additive noise (topk_noise_type 'gumbel',
  * model_mulan_epsilon.py:236-239); gnoise = NULL: hard k-hot of the plain logits (soft / nrm may be NULL). */

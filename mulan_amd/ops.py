@@ -2368,6 +2368,72 @@ def bound_profile(mode, x, g0, g1, gt, w, eps0, eps, zt, net, rows_per_group, ro
     return rows_out, cols_out
 
 
+KNN_MAX_K = 16
+KNN_EMPTY = (2 ** 31 - 1, -1)      # (dist2, idx) of a slot no reference qualified for
+
+
+def knn_check(q, r, k, idx_base=0, self_offset=-1, out=None, radius2=None, covered=None, splits=0):
+    """every check of knn_u8 that needs no library call; q, r: anything with dtype, shape (and, for tensors, device)"""
+    for name, v in (("q", q), ("r", r)):
+        if not hasattr(v, "dtype") or str(v.dtype) not in ("torch.uint8", "uint8") or len(v.shape) != 2 or v.shape[0] < 1:
+            raise ValueError(f"knn_u8: {name} is uint8 [rows >= 1, D]; got "
+                             f"{(v.dtype, tuple(v.shape)) if hasattr(v, 'dtype') else type(v).__name__}")
+    Q, D = q.shape
+    N = r.shape[0]
+    if r.shape[1] != D:
+        raise ValueError(f"knn_u8: q has D = {D}, r has D = {r.shape[1]}")
+    if D % 64 or not 64 <= D <= 16384:
+        raise ValueError(f"knn_u8: D is a multiple of 64 in [64, 16384], got {D}")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"knn_u8: k is an int in [1, {KNN_MAX_K}], got {k!r}")
+    if idx_base < 0 or idx_base + N > 2 ** 31 - 1:
+        raise ValueError(f"knn_u8: idx_base >= 0 and idx_base + N <= 2^31 - 1, got idx_base = {idx_base}, N = {N}")
+    if self_offset < -1:
+        raise ValueError(f"knn_u8: self_offset is -1 (none) or >= 0, got {self_offset}")
+    if not 0 <= splits <= 4096:
+        raise ValueError(f"knn_u8: splits is 0 (the library chooses) or in [1, 4096], got {splits}")
+    if covered is not None and radius2 is None:
+        raise ValueError("knn_u8: covered is an output of the radius mode and needs radius2")
+    if radius2 is not None and (not torch.is_tensor(radius2) or radius2.dtype != torch.int32 or tuple(radius2.shape) != (N,)):
+        raise ValueError(f"knn_u8: radius2 is int32 [{N}]")
+    if covered is not None and (not torch.is_tensor(covered) or covered.dtype != torch.uint8 or tuple(covered.shape) != (Q,)):
+        raise ValueError(f"knn_u8: covered is uint8 [{Q}]")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("knn_u8: out is the pair (dist2, idx) of an earlier call")
+        for name, v in zip(("dist2", "idx"), out):
+            if not torch.is_tensor(v) or v.dtype != torch.int32 or tuple(v.shape) != (Q, k) or not v.is_contiguous():
+                raise ValueError(f"knn_u8: out's {name} is a contiguous int32 [{Q}, {k}]")
+    return Q, N, D
+
+
+def knn_u8(q, r, k, idx_base=0, self_offset=-1, out=None, radius2=None, covered=None, splits=0):
+    """(dist2, idx), int32 [Q, k]: for every row of q (uint8 [Q, D]) the k smallest squared Euclidean distances to the rows of
+    r (uint8 [N, D]), ascending, and the rows' indices + idx_base; exact integers from the int8 matrix cores
+    (mulan_knn_u8).  Equal distances go to the smaller index; slots no reference qualified for hold KNN_EMPTY.
+    self_offset >= 0 leaves out the pair with j + idx_base == i + self_offset.  out = (dist2, idx) of earlier calls:
+    this call's references are merged into those lists, in place (a reference set walked in chunks).
+    radius2 (int32 [N]): also returns covered (uint8 [Q]), 1 where some qualifying j has d2(i, j) <= radius2[j]; a
+    `covered` passed in is OR-ed into (only together with out, or it is overwritten).  splits: slices of the reference
+    range, 0 for the library's choice; the result does not depend on it."""
+    Q, N, D = knn_check(q, r, k, idx_base, self_offset, out, radius2, covered, splits)
+    if not torch.is_tensor(q) or not torch.is_tensor(r) or q.device != r.device:
+        raise ValueError("knn_u8: q and r are tensors on one device")
+    dev = q.device
+    for name, v in (("radius2", radius2), ("covered", covered), ("dist2", out and out[0]), ("idx", out and out[1])):
+        if v is not None and v.device != dev:
+            raise ValueError(f"knn_u8: {name} is on {v.device}, q on {dev}")
+    q, r, radius2 = _c(q), _c(r), _c(radius2)
+    accumulate = out is not None
+    dist2, idx = out if accumulate else (torch.empty((Q, k), device=dev, dtype=torch.int32) for _ in range(2))
+    if radius2 is not None and covered is None:
+        covered = torch.zeros(Q, device=dev, dtype=torch.uint8)
+    ws = torch.empty(lib.load().mulan_knn_u8_workspace(Q, k, int(splits)) // 8 + 1, device=dev, dtype=torch.int64)
+    call("mulan_knn_u8", ptr(q), ptr(r), Q, N, D, k, int(idx_base), int(self_offset), int(accumulate), int(splits),
+         ptr(radius2), ptr(covered), ptr(dist2), ptr(idx), ptr(ws), stream())
+    return (dist2, idx) if radius2 is None else (dist2, idx, covered)
+
+
 # ----------------------------------------------------------------------------- exact-likelihood ODE (eval only)
 def topk_hard(logits, k):
     """(k-hot embedding of the plain logits, KL(softmax(logits) || uniform)): notebook_utils.logits_to_embeddings and
