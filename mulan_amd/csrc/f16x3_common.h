@@ -1,5 +1,5 @@
-// Shared pieces of the f16x3 kernels (conv3x3_f16x3.hip, conv3x3_f16x3_v3.hip): operand scales, the fp32 -> 2 x fp16
-// split, the maxima format and the argument block of the forward / input-gradient convolution.
+// Shared pieces of the f16x3 kernels (conv3x3_f16x3.hip, conv3x3_f16x3_v3.hip, wgrad_f16x3.hip, f16x3_prep.hip): operand
+// scales, the fp32 -> 2 x fp16 split, the maxima format and the argument block of the forward / input-gradient convolution.
 #pragma once
 #include "common.h"
 

@@ -155,6 +155,17 @@ def _wgrad_to_sink(sink, launch, keep, ok=True):
     return launch(out=_fresh(sink) if sink is not None else None)
 
 
+def _maxima_slots(B, blocks, dev, want=True):
+    """the optional [B, MAX_PARTS] maxima by-product of a launch with `blocks` blocks per image (one slot each): None
+    where the slots do not suffice, or where the caller does not `want` it"""
+    return torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32) if want and blocks <= MAX_PARTS else None
+
+
+def _leave_maxima(t, maxima):
+    """the counterpart of _maxima_slots: leaves the array the launch filled, if there was one, on its output; returns t"""
+    return t if maxima is None else _leave(t, "_absmax", maxima)
+
+
 def absmax_rows(x):
     """[B,16] int32: fp32 bit patterns of 16 partial maxima of |x[b]| (the per-image maximum is the max of a row);
     they feed the per-image operand scales of the f16x3 kernels"""
@@ -453,12 +464,11 @@ def conv3x3_raw(x, w, bias=None, cbias=None, res=None, xmax=None, planes=False, 
         xmax = absmax_rows(x)
     xs = torch.empty(B * HW * C * 4, device=x.device, dtype=torch.uint8) if planes else None
     # by-product: the maxima of y, left on the tensor for whichever f16x3 kernel reads it next
-    ymax = torch.empty((B, MAX_PARTS), device=x.device, dtype=torch.int32) if (H // 8) * (N // 128) <= MAX_PARTS else None
+    ymax = _maxima_slots(B, (H // 8) * (N // 128), x.device)
     _timed("conv3x3_f16x3_kernel", flops,
            lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(x), ptr(xmax), ptr(wp), ptr(wmax), ptr(bias), ptr(cbias), mode,
                         ptr(res), ptr(y), ptr(xs), ptr(ymax), _alone(), B, H, W, C, N, stream()))
-    if ymax is not None:
-        _leave(y, "_absmax", ymax)
+    _leave_maxima(y, ymax)
     return (y, xs) if planes else y
 
 
@@ -475,13 +485,11 @@ def conv3x3_dgrad_raw(dy, w, dymax=None, planes=False, wmax=None, want_max=False
         if dymax is None:
             dymax = absmax_rows(dy)
         dys = torch.empty(B * HW * N * 4, device=dy.device, dtype=torch.uint8) if planes else None
-        dxmax = (torch.empty((B, MAX_PARTS), device=dy.device, dtype=torch.int32)
-                 if want_max and (H // 8) * (C // 128) <= MAX_PARTS else None)
+        dxmax = _maxima_slots(B, (H // 8) * (C // 128), dy.device, want_max)
         _timed("conv3x3_f16x3_kernel", flops,
                lambda: call("mulan_conv3x3_fwd_f16x3_alone", ptr(dy), ptr(dymax), ptr(wp), ptr(wmax), None, None, 0, None,
                             ptr(dx), ptr(dys), ptr(dxmax), _alone(), B, H, W, N, C, stream()))
-        if dxmax is not None:
-            _leave(dx, "_absmax", dxmax)
+        _leave_maxima(dx, dxmax)
         return (dx, dys) if planes else dx
     wT = torch.empty((3, 3, N, C), device=w.device, dtype=torch.float32)
     call("mulan_conv3x3_wflip", ptr(w), ptr(wT), C, N, stream())
@@ -495,8 +503,7 @@ def conv3x3_dgrad_planes_raw(dys, dymax, w, wmax=None, want_max=False):
     B = dymax.shape[0]
     dx = torch.empty((B, HW, C), device=dys.device, dtype=torch.float32)
     wp, wmax = _pack_weights(w, C, N, 1, wmax)
-    dxmax = (torch.empty((B, MAX_PARTS), device=dys.device, dtype=torch.int32)
-             if want_max and (H // 8) * (C // 128) <= MAX_PARTS else None)
+    dxmax = _maxima_slots(B, (H // 8) * (C // 128), dys.device, want_max)
     # alone: no weight-gradient stream beside this launch (the ODE evaluator's vector-Jacobian product, not the backward
     # pass of a train step -- with or without MULAN_SIDE_STREAM, so that both modes sum in the same order): small launches
     # may then run as k-split blocks (conv3x3_f16x3_v3.hip)
@@ -504,9 +511,7 @@ def conv3x3_dgrad_planes_raw(dys, dymax, w, wmax=None, want_max=False):
     _timed("conv3x3_f16x3_kernel<planes_in,dgrad>", 2.0 * B * HW * 9 * C * N,
            lambda: call("mulan_conv3x3_fwd_f16x3_planes_in_stats", ptr(dys), ptr(dymax), ptr(wp), ptr(wmax), None, None, 0,
                         None, ptr(dx), ptr(dxmax), None, alone, B, H, W, N, C, stream()))
-    if dxmax is not None:
-        _leave(dx, "_absmax", dxmax)
-    return dx
+    return _leave_maxima(dx, dxmax)
 
 
 def grad_planes_eligible(C, N):
@@ -538,35 +543,34 @@ def _fresh(view):
     return view.view(view.shape)
 
 
+def _wgrad_launch(name, fn, operands, B, C, N, taps, out, dev, share=None, dims=None):
+    """what the slab weight-gradient launches share: the workspace that `fn`_workspace asks for, dw (`out`, or a fresh
+    [3,3,C,N] for taps = 9, [C,N] for taps = 1) and the timed call fn(*operands, dw, workspace, *dims, accumulate = 0
+    [, share]); dims = (B, H, W, C, N) unless the entry point takes another list.  Returns dw."""
+    tail = () if share is None else (share,)
+    nbytes = getattr(lib.load(), fn + "_workspace")(B, H, W, C, N, *tail)
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    dw = out if out is not None else torch.empty((3, 3, C, N) if taps == 9 else (C, N), device=dev, dtype=torch.float32)
+    dims = (B, H, W, C, N) if dims is None else dims
+    _timed(name, 2.0 * B * HW * taps * C * N, lambda: call(fn, *operands, ptr(dw), ptr(ws), *dims, 0, *tail, stream()))
+    return dw
+
+
 def conv3x3_wgrad_raw(x, dy, out=None, xmax=None, dymax=None):
     B, C, N = x.shape[0], x.shape[-1], dy.shape[-1]
-    fast = CONV_MODE == "f16x3" and C % 4 == 0 and N % 4 == 0
-    fn = "mulan_conv3x3_wgrad" + ("_f16x3" if fast else "")
-    nbytes = getattr(lib.load(), fn + "_workspace")(B, H, W, C, N)
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
-    dw = out if out is not None else torch.empty((3, 3, C, N), device=x.device, dtype=torch.float32)
-    name = "conv3x3_wgrad" + ("_f16x3" if fast else "") + "_kernel+slab_reduce"
-    flops = 2.0 * B * HW * 9 * C * N
-    if fast:
+    infix, operands = "", (ptr(x), ptr(dy))
+    if CONV_MODE == "f16x3" and C % 4 == 0 and N % 4 == 0:
         xmax = absmax_rows(x) if xmax is None else xmax
         dymax = absmax_rows(dy) if dymax is None else dymax
-        _timed(name, flops, lambda: call(fn, ptr(x), ptr(xmax), ptr(dy), ptr(dymax), ptr(dw), ptr(ws), B, H, W, C, N, 0,
-                                         stream()))
-    else:
-        _timed(name, flops, lambda: call(fn, ptr(x), ptr(dy), ptr(dw), ptr(ws), B, H, W, C, N, 0, stream()))
-    return dw
+        infix, operands = "_f16x3", (ptr(x), ptr(xmax), ptr(dy), ptr(dymax))
+    return _wgrad_launch("conv3x3_wgrad" + infix + "_kernel+slab_reduce", "mulan_conv3x3_wgrad" + infix, operands, B, C, N, 9,
+                         out, x.device)
 
 
 def conv3x3_wgrad_planes_raw(xs, xmax, dys, dymax, B, C, N, out=None):
     """dw from the split planes of x (written by the forward conv) and of dy (written by the input-gradient conv)"""
-    share = _share_chip()
-    nbytes = lib.load().mulan_conv3x3_wgrad_f16x3_planes_workspace(B, H, W, C, N, share)
-    ws = torch.empty(nbytes // 4, device=xs.device, dtype=torch.float32)
-    dw = out if out is not None else torch.empty((3, 3, C, N), device=xs.device, dtype=torch.float32)
-    _timed("conv3x3_wgrad_f16x3_planes_kernel+slab_reduce", 2.0 * B * HW * 9 * C * N,
-           lambda: call("mulan_conv3x3_wgrad_f16x3_planes", ptr(xs), ptr(xmax), ptr(dys), ptr(dymax), ptr(dw), ptr(ws), B,
-                        H, W, C, N, 0, share, stream()))
-    return dw
+    return _wgrad_launch("conv3x3_wgrad_f16x3_planes_kernel+slab_reduce", "mulan_conv3x3_wgrad_f16x3_planes",
+                         (ptr(xs), ptr(xmax), ptr(dys), ptr(dymax)), B, C, N, 9, out, xs.device, _share_chip())
 
 
 def gemm_raw(A, Bm, M, N, K, *, bias=None, R=None, transA=False, transB=False, alpha=1.0, beta=1.0,
@@ -805,14 +809,8 @@ def linear_f16x3_raw(x1, x2, wp, wmax, N1, N2, bias=None, res=None, planes=False
 def linear_wgrad_planes_raw(xs, xmax, dys, dymax, B, K, N, out=None):
     """dw[K,N] = [x1|x2]^T dy from the planes handed on by linear_f16x3_raw (xs) and by the convolution that consumed
     the same dy (dys)"""
-    share = _share_chip()
-    nbytes = lib.load().mulan_linear_wgrad_f16x3_planes_workspace(B, H, W, K, N, share)
-    ws = torch.empty(nbytes // 4, device=xs.device, dtype=torch.float32)
-    dw = out if out is not None else torch.empty((K, N), device=xs.device, dtype=torch.float32)
-    _timed("linear_wgrad_f16x3_planes_kernel+slab_reduce", 2.0 * B * HW * K * N,
-           lambda: call("mulan_linear_wgrad_f16x3_planes", ptr(xs), ptr(xmax), ptr(dys), ptr(dymax), ptr(dw), ptr(ws), B, H,
-                        W, K, N, 0, share, stream()))
-    return dw
+    return _wgrad_launch("linear_wgrad_f16x3_planes_kernel+slab_reduce", "mulan_linear_wgrad_f16x3_planes",
+                         (ptr(xs), ptr(xmax), ptr(dys), ptr(dymax)), B, K, N, 1, out, xs.device, _share_chip())
 
 
 def linear_wgrad_x32_raw(x1, x2, xmax, xmax2, dys, dymax, B, N, out=None):
@@ -822,14 +820,9 @@ def linear_wgrad_x32_raw(x1, x2, xmax, xmax2, dys, dymax, B, N, out=None):
     linear_wgrad_planes_raw on the planes the forward kernel would have written -- which it then need not write."""
     K1 = x1.shape[-1]
     K2 = 0 if x2 is None else x2.shape[-1]
-    share = _share_chip()
-    nbytes = lib.load().mulan_linear_wgrad_f16x3_x32_workspace(B, H, W, K1 + K2, N, share)
-    ws = torch.empty(nbytes // 4, device=x1.device, dtype=torch.float32)
-    dw = out if out is not None else torch.empty((K1 + K2, N), device=x1.device, dtype=torch.float32)
-    _timed("linear_wgrad_f16x3_planes_kernel+slab_reduce", 2.0 * B * HW * (K1 + K2) * N,
-           lambda: call("mulan_linear_wgrad_f16x3_x32", ptr(x1), ptr(x2), K1, K2, ptr(xmax), ptr(xmax2), ptr(dys), ptr(dymax), ptr(dw),
-                        ptr(ws), B, H, W, N, 0, share, stream()))
-    return dw
+    return _wgrad_launch("linear_wgrad_f16x3_planes_kernel+slab_reduce", "mulan_linear_wgrad_f16x3_x32",
+                         (ptr(x1), ptr(x2), K1, K2, ptr(xmax), ptr(xmax2), ptr(dys), ptr(dymax)), B, K1 + K2, N, 1, out,
+                         x1.device, _share_chip(), dims=(B, H, W, N))
 
 
 # the dense weight gradient reads the layer's fp32 input and splits it in its staging path (round 3) instead of taking
@@ -1115,13 +1108,11 @@ def _gn_forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset):
     mean = torch.empty((B, groups), device=x1.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
     # by-product for a following f16x3 convolution: the per-image maxima of y
-    ymax = (torch.empty((B, MAX_PARTS), device=x1.device, dtype=torch.int32)
-            if CONV_MODE == "f16x3" and (C1 + C2) // 32 <= MAX_PARTS else None)
+    ymax = _maxima_slots(B, (C1 + C2) // 32, x1.device, CONV_MODE == "f16x3")
     sv, sd = _seed_args(seed)
     call("mulan_groupnorm_fwd_dyn", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), B,
          HW, groups, float(eps), int(act), float(keep), sv, int(offset), ptr(sd), ptr(ymax), stream())
-    if ymax is not None:
-        _leave(y, "_absmax", ymax)
+    _leave_maxima(y, ymax)
     ctx.save_for_backward(x1, x2, gamma, beta, mean, rstd)
     ctx.meta = (groups, int(act), float(keep), seed, int(offset))
     ctx.gv = (_gv(gamma), _gv(beta))
@@ -1319,7 +1310,7 @@ def _conv_outputs(B, N, dev, bias, cbias, res, want_stats):
     more blocks per image than maxima slots), the cbias mode, contiguous bias / cbias / res, and -- want_stats -- ystats:
     one row of partial sums per row tile of that launch (8, 4 or 2 image rows) for the GroupNorm behind it"""
     y = torch.empty((B, HW, N), device=dev, dtype=torch.float32)
-    ymax = torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32) if (H // 8) * (N // 128) <= MAX_PARTS else None
+    ymax = _maxima_slots(B, (H // 8) * (N // 128), dev)
     mode = 0 if cbias is None else (1 if cbias.dim() == 2 else 2)
     bias_c, cb_c, res_c = _c(bias), _c(cbias), _c(res)
     ystats = None
@@ -1441,8 +1432,7 @@ class GnConv3x3Fn(torch.autograd.Function):
                         skip, mode):
         B, C1 = x1.shape[0], x1.shape[-1]
         Ct, N = C1 + (0 if x2 is None else x2.shape[-1]), w.shape[-1]
-        if ymax is not None:
-            _leave(y, "_absmax", ymax)
+        _leave_maxima(y, ymax)
         if ystats is not None:
             _leave(y, "_gnstats", ystats)
         ctx.save_for_backward(x1, x2, gamma, beta, mean, rstd, ys, w, bound)
