@@ -640,6 +640,32 @@ size_t mulan_knn_u8_workspace(int Q, int k, int splits);
 int mulan_knn_u8(const unsigned char* q, const unsigned char* r, int Q, int N, int D, int k, int idx_base,
                  int self_offset, int accumulate, int splits, const int* radius2, unsigned char* covered, int* dist2,
                  int* idx, void* workspace, mulan_stream_t stream);
+/* Spatial spectra of N images of 32 x 32 x 3, channels innermost (spectrum.hip): per image and plane the orthonormal
+ * 2-D DCT-II Y = D X D^T, D[u][y] = c_u cos(pi (2 y + 1) u / 64), c_0 = sqrt(1 / 32), c_u = sqrt(2 / 32) otherwise -- what
+ * scipy.fft.dctn(x, norm='ortho') gives -- on the fp32 matrix cores.  u is the vertical frequency, v the horizontal one.
+ *   x, dtype      dtype 0: uint8 [N][32][32][3], read as scale * v + offset; dtype 1: fp32 of that shape, taken as is
+ *   gray          1: the three channels are mixed into one plane, 0.2125 R + 0.7154 G + 0.0721 B, before the transform.
+ *                 P = 1 with gray, else 3 (plane p is channel p).
+ * Each output may be NULL, not all:
+ *   coef [N][32][32][P]   Y[u][v] of image n and plane p
+ *   radial [N][45][P]     the sum of Y^2 over the (u, v) of radial bin r: r^2 - r < u^2 + v^2 <= r^2 + r, which is
+ *                         r = floor(sqrt(u^2 + v^2) + 1/2); bin 0 is the DC term alone
+ *   sum1, sum2 [32][32][P]  fp64: the sums over n of Y and of Y^2; accumulate = 1 adds them to what the arrays hold (a
+ *                         set walked in chunks), 0 overwrites
+ *   blocks        0: the library chooses how many blocks share the images (min(N, 1024)); 1..4096: at most that many.
+ *                 coef and radial do not depend on it; sum1 and sum2 are added up per block first, so only their
+ *                 rounding does.
+ *   workspace     mulan_spectrum_workspace(N, gray, blocks) bytes (0 for arguments that are refused), 8-byte aligned;
+ *                 read only with sum1 or sum2
+ * Every sum is taken in one fixed order and there are no atomics: the same arguments give the same bits.  x and coef
+ * must be 16-byte aligned, radial 4-byte, sum1 and sum2 8-byte.
+ * hipErrorInvalidValue, before anything is launched, for N < 1, a NULL x, all four outputs NULL, accumulate with
+ * neither sum1 nor sum2, sum1 or sum2 with a NULL workspace or workspace_bytes below mulan_spectrum_workspace(N, gray,
+ * blocks), dtype, gray or accumulate outside 0..1, blocks outside 0..4096, a misaligned pointer. */
+size_t mulan_spectrum_workspace(int N, int gray, int blocks);
+int mulan_spectrum(const void* x, int dtype, float scale, float offset, int N, int gray, float* coef, float* radial,
+                   double* sum1, double* sum2, int accumulate, int blocks, void* workspace, size_t workspace_bytes,
+                   mulan_stream_t stream);
 /* _topk_embedding_and_loss + _gamma_noise + _gumbel_kl_loss (model_mulan_velocity.py:78-120).
  * gnoise: [10,B,L] raw Gamma(1/k,1) draws; tau < 0: gnoise is [B,L] additive noise (topk_noise_type 'gumbel',
  * model_mulan_epsilon.py:236-239); gnoise = NULL: hard k-hot of the plain logits (soft / nrm may be NULL). */

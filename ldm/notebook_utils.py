@@ -1,7 +1,9 @@
 """Evaluators of the reference's ldm/notebook_utils.py: Experiment_Colab (:28-39, EMA parameters of a checkpoint),
 the variational-bound BPD evaluators (:157-191), the exact-likelihood ODE evaluator (:232-373, 446-531) and the views of
 the learned noise schedule (:554-711); bound_profile / plot_bound_profile (not in the reference) take the bound apart;
-nearest_neighbours / sample_novelty / precision_recall / plot_neighbours (not in the reference) ask whether samples are new."""
+nearest_neighbours / sample_novelty / precision_recall / plot_neighbours (not in the reference) ask whether samples are new;
+dct2 (:730-733, there on skimage and scipy) and image_spectrum / compare_spectra / schedule_spectrum / plot_spectra (not
+in the reference) look at spatial frequency."""
 from mulan_amd.evaluators import (Experiment_Colab, Hutchinson, eval_bpd_dense_sampling,  # noqa: F401
                                   eval_bpd_ode, eval_bpd_sparse_sampling, get_ode_likelihood_fn, get_logits, get_sample_fn,
                                   logits_to_embeddings, _get_bpd_offset)
@@ -10,3 +12,5 @@ from mulan_amd.evaluators import (Clustering, get_embedding, heat_map_panels, no
 from mulan_amd.evaluators import bound_profile, plot_bound_profile  # noqa: F401
 from mulan_amd.neighbours import nearest as nearest_neighbours, novelty as sample_novelty  # noqa: F401
 from mulan_amd.neighbours import precision_recall, plot_neighbours  # noqa: F401
+from mulan_amd.spectrum import (compare_spectra, dct2, image_spectrum, plot_spectra,  # noqa: F401
+                                schedule_spectrum)

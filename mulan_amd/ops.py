@@ -2424,6 +2424,70 @@ def knn_u8(q, r, k, idx_base=0, self_offset=-1, out=None, radius2=None, covered=
     return (dist2, idx) if radius2 is None else (dist2, idx, covered)
 
 
+SPECTRUM_BINS = 45                 # radial bins of a 32 x 32 DCT: floor(sqrt(u^2 + v^2) + 1/2) = 0 .. 44
+SPECTRUM_GRAY = (0.2125, 0.7154, 0.0721)   # skimage.color.rgb2gray; the kernel holds the same constants
+
+
+def spectrum_check(x, scale=1.0, offset=0.0, gray=False, coef=False, radial=False, sums=False, accumulate_into=None,
+                   blocks=0):
+    """every check of spectrum that needs no library call; x: anything with dtype and shape -> (N, P)"""
+    if not hasattr(x, "dtype") or str(x.dtype) not in ("torch.uint8", "uint8", "torch.float32", "float32") \
+            or len(x.shape) != 4 or tuple(x.shape[1:]) != (32, 32, 3) or x.shape[0] < 1:
+        raise ValueError(f"spectrum: x is uint8 or fp32 [N >= 1, 32, 32, 3]; got "
+                         f"{(x.dtype, tuple(x.shape)) if hasattr(x, 'dtype') else type(x).__name__}")
+    for name, v in (("scale", scale), ("offset", offset)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+            raise ValueError(f"spectrum: {name} is a finite number, got {v!r}")
+    for name, v in (("gray", gray), ("coef", coef), ("radial", radial), ("sums", sums)):
+        if not isinstance(v, bool):
+            raise ValueError(f"spectrum: {name} is a bool, got {v!r}")
+    if isinstance(blocks, bool) or not isinstance(blocks, int) or not 0 <= blocks <= 4096:
+        raise ValueError(f"spectrum: blocks is 0 (the library chooses) or in [1, 4096], got {blocks!r}")
+    P = 1 if gray else 3
+    if accumulate_into is not None:
+        if not isinstance(accumulate_into, (tuple, list)) or len(accumulate_into) != 2:
+            raise ValueError("spectrum: accumulate_into is the pair (sum1, sum2) of an earlier call")
+        for name, v in zip(("sum1", "sum2"), accumulate_into):
+            if not torch.is_tensor(v) or v.dtype != torch.float64 or tuple(v.shape) != (32, 32, P) or not v.is_contiguous():
+                raise ValueError(f"spectrum: accumulate_into's {name} is a contiguous fp64 [32, 32, {P}]")
+    if not (coef or radial or sums or accumulate_into is not None):
+        raise ValueError("spectrum: nothing asked for (coef, radial and sums are all off)")
+    return x.shape[0], P
+
+
+def spectrum(x, *, scale=1.0, offset=0.0, gray=False, coef=False, radial=False, sums=False, accumulate_into=None, blocks=0):
+    """(coef | None, radial | None, (sum1, sum2) | None) of N images x [N, 32, 32, 3]: the orthonormal 2-D DCT-II of every
+    image and plane, scipy.fft.dctn(norm='ortho'), on the fp32 matrix cores (mulan_spectrum).  uint8 x is read as
+    scale v + offset, fp32 x as it is; gray mixes the channels (SPECTRUM_GRAY) into one plane first: P = 1, else 3.
+    coef: fp32 [N, 32, 32, P], [n, u, v, p] with u the vertical frequency.  radial: fp32 [N, 45, P], the sum of coef^2
+    over radial bin r = floor(sqrt(u^2 + v^2) + 1/2).  sums: fp64 [32, 32, P] each, the sums over n of coef and coef^2.
+    accumulate_into = (sum1, sum2) of an earlier call: this call's images are added to them, in place, and they are
+    returned (a set uploaded in chunks).  blocks: 0 for the library's choice; only the rounding of the sums depends on
+    it.  One fixed order per sum: the same call gives the same bits."""
+    N, P = spectrum_check(x, scale, offset, gray, coef, radial, sums, accumulate_into, blocks)
+    if not torch.is_tensor(x):
+        raise ValueError("spectrum: x is a tensor on the device")
+    dev = x.device
+    if accumulate_into is not None and any(v.device != dev for v in accumulate_into):
+        raise ValueError(f"spectrum: accumulate_into is on {accumulate_into[0].device}, x on {dev}")
+    x = _c(x)
+    coef_out = torch.empty((N, 32, 32, P), device=dev, dtype=torch.float32) if coef else None
+    radial_out = torch.empty((N, SPECTRUM_BINS, P), device=dev, dtype=torch.float32) if radial else None
+    sum1 = sum2 = ws = None
+    nbytes = 0
+    if accumulate_into is not None:
+        sum1, sum2 = accumulate_into
+    elif sums:
+        sum1, sum2 = (torch.empty((32, 32, P), device=dev, dtype=torch.float64) for _ in range(2))
+    if sum1 is not None:
+        nbytes = lib.load().mulan_spectrum_workspace(N, int(gray), int(blocks))
+        ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    call("mulan_spectrum", ptr(x), 0 if x.dtype == torch.uint8 else 1, float(scale), float(offset), N, int(gray),
+         ptr(coef_out), ptr(radial_out), ptr(sum1), ptr(sum2), int(accumulate_into is not None), int(blocks), ptr(ws),
+         nbytes, stream())
+    return coef_out, radial_out, (sum1, sum2) if sum1 is not None else None
+
+
 # ----------------------------------------------------------------------------- exact-likelihood ODE (eval only)
 def topk_hard(logits, k):
     """(k-hot embedding of the plain logits, KL(softmax(logits) || uniform)): notebook_utils.logits_to_embeddings and
