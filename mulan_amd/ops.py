@@ -8,6 +8,7 @@ _leave / _left / _carry below; DESIGN.md section 2 ("By-products travel with the
 """
 import math
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -27,6 +28,12 @@ CONV_MODES = ("f16x3", "f32")
 CONV_MODE = _os.environ.get("MULAN_CONV_MODE", "f16x3")
 if CONV_MODE not in CONV_MODES:
     raise ValueError(f"MULAN_CONV_MODE must be one of {', '.join(CONV_MODES)}; got {CONV_MODE!r}")
+
+
+def _flag(name, default):
+    """the import-time value of an on/off switch: the environment variable MULAN_<name> ("1" = on), else `default`.  The
+    switch itself is the module attribute the result is assigned to, read wherever it is used."""
+    return _os.environ.get("MULAN_" + name, default) == "1"
 
 
 def _c(t):
@@ -61,7 +68,7 @@ MAX_PARTS = 16
 # a sink in the flat gradient buffer take this path (nothing on the main stream reads them before side_join()).
 # Scope: `with weight_gradient_stream(): loss.backward()` (the train step does this); outside such a block everything
 # stays on the current stream.
-SIDE_STREAM = _os.environ.get("MULAN_SIDE_STREAM", "1") == "1"
+SIDE_STREAM = _flag("SIDE_STREAM", "1")
 # side launches whose operands are kept alive before the main stream waits for the oldest (2: +1.0 ms, 16: +0.2 ms per step)
 SIDE_DEPTH = int(_os.environ.get("MULAN_SIDE_DEPTH", "6"))
 # While the weight-gradient launches share the chip with the input-gradient chain they aim for 120 blocks instead of
@@ -70,7 +77,7 @@ SIDE_DEPTH = int(_os.environ.get("MULAN_SIDE_DEPTH", "6"))
 # main stream; with 120 the launch takes about as long as the main stream's kernels of the same layer (GroupNorm
 # backward + input-gradient convolution) and both streams keep running side by side: -2.9 % per step (scan 96 ... 240,
 # profiles/DESIGN_r04.md 3.2).  MULAN_SIDE_WGRAD_SHARE=0 keeps 240.
-SIDE_WGRAD_SHARE = _os.environ.get("MULAN_SIDE_WGRAD_SHARE", "1") == "1"
+SIDE_WGRAD_SHARE = _flag("SIDE_WGRAD_SHARE", "1")
 _SIDE = {"stream": None, "pending": None, "active": False, "scope": False}
 
 
@@ -239,7 +246,7 @@ def view_keep_absmax(x, *shape):
     return _carry(x, x.view(*shape), tags=("_absmax",))
 
 
-TEE_COLSUM = _os.environ.get("MULAN_TEE_COLSUM", "1") == "1"     # A/B switch: 0 = the bias gradient takes its own pass
+TEE_COLSUM = _flag("TEE_COLSUM", "1")     # A/B switch: 0 = the bias gradient takes its own pass
 
 
 class TeeFn(torch.autograd.Function):
@@ -277,7 +284,7 @@ class TeeFn(torch.autograd.Function):
 # The gradient sum of a block output with two consumers inside the GroupNorm backward kernel of the first consumer
 # (mulan_groupnorm_bwd_fused, add1b) instead of in a kernel of its own (TeeFn): the skip-connection gradient, which the
 # backward pass produces first, waits in a box until that kernel runs.  A/B switch: 0 = TeeFn.
-TEE_MAILBOX = _os.environ.get("MULAN_TEE_MAILBOX", "1") == "1"
+TEE_MAILBOX = _flag("TEE_MAILBOX", "1")
 
 
 class _GradBox:
@@ -440,6 +447,16 @@ def planes_eligible(C, N):
     return CONV_MODE == "f16x3" and C % 128 == 0 and N % 128 == 0
 
 
+def _cbias_mode(cbias):
+    """the cbias mode of the convolution entry points: 0 none, 1 per sample [B,N], 2 per pixel [B,1024,N]"""
+    return 0 if cbias is None else (1 if cbias.dim() == 2 else 2)
+
+
+def _has(bias, cbias, res):
+    """which of a convolution's optional addends exist, as its backward reads it: (bias?, cbias.dim() or None, res?)"""
+    return bias is not None, None if cbias is None else cbias.dim(), res is not None
+
+
 def conv3x3_raw(x, w, bias=None, cbias=None, res=None, xmax=None, planes=False, wmax=None):
     """x [B,1024,C], w [3,3,C,N] -> [B,1024,N]   (xmax: absmax_rows(x) if the caller already has it, f16x3 mode).
     planes=True (f16x3 mode): returns (y, xs) with xs the split fp16 planes of x for conv3x3_wgrad_planes_raw."""
@@ -447,9 +464,7 @@ def conv3x3_raw(x, w, bias=None, cbias=None, res=None, xmax=None, planes=False, 
     B, C, N = x.shape[0], x.shape[-1], w.shape[-1]
     assert w.shape[:3] == (3, 3, C), (w.shape, C)
     y = torch.empty((B, HW, N), device=x.device, dtype=torch.float32)
-    mode = 0
-    if cbias is not None:
-        mode = 1 if cbias.dim() == 2 else 2
+    mode = _cbias_mode(cbias)
     fast = CONV_MODE == "f16x3" and C % 16 == 0 and N % 128 == 0
     flops = 2.0 * B * HW * 9 * C * N
     if not fast:
@@ -614,37 +629,49 @@ def randn(shape, seed, offset, device, out=None):
 
 
 # ----------------------------------------------------------------------------- conv
+class _ConvBwd(NamedTuple):
+    """what _conv3x3_backward reads.  Conv3x3Fn and GnConv3x3Fn build it in forward, where every field is known; the
+    tensors that go through save_for_backward (`saved`, and GnConv3x3Fn's `xmax`) are emptied out of the copy kept on the
+    context and put back at the top of backward."""
+    saved: tuple                   # (x, or its split planes where `planes`, w)
+    planes: bool                   # saved[0] is the plane tensor: plane-fed weight gradient, dy's planes handed on
+    xmax: Optional[torch.Tensor]   # maxima (or the a-priori bound) the forward kernel scaled x with; None: fp32 kernels
+    wmax: Optional[torch.Tensor]
+    has: tuple                     # _has(bias, cbias, res)
+    gv: tuple                      # (_gv(w), _gv(bias)): the gradient sinks
+    need: tuple                    # needs_input_grad of (x, w, bias, cbias, res)
+    want_dx_max: bool = False      # the kernel leaves the maxima of dx on it (for a GroupNorm backward that writes planes)
+
+
 class Conv3x3Fn(torch.autograd.Function):
     """y = conv3x3(x, w) + bias + cbias + res   (ldm/model_vdm.py:633-656)"""
 
     @staticmethod
     def forward(ctx, x, w, bias, cbias, res):
         x, w = _c(x), _c(w)
+        need = ctx.needs_input_grad
         f16 = CONV_MODE == "f16x3" and x.shape[-1] % 4 == 0        # per-image maxima: shared by fwd and wgrad
         xmax = cached_absmax(x) if f16 else None
         pre = _prepacked(w, 0)
         wmax = (pre[1] if pre is not None else absmax_rows(w.view(1, -1))) if f16 else None   # shared by both packs
-        ctx.wmax = wmax
         # the forward kernel hands its split input planes to the weight-gradient kernel: saved instead of x (same bytes)
-        ctx.planes = planes_eligible(x.shape[-1], w.shape[-1]) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
-        if ctx.planes:
-            y, xs = conv3x3_raw(x, w, _c(bias), _c(cbias), _c(res), xmax=xmax, planes=True, wmax=wmax)
-            ctx.save_for_backward(xs, w)
-            ctx.xshape = x.shape
-        else:
-            y = conv3x3_raw(x, w, _c(bias), _c(cbias), _c(res), xmax=xmax, wmax=wmax)
-            ctx.save_for_backward(x, w)
-        ctx.xmax = xmax
-        ctx.has = (bias is not None, None if cbias is None else cbias.dim(), res is not None)
-        ctx.gv = (_gv(w), _gv(bias))
-        if ctx.gv[1] is not None and ctx.needs_input_grad[2]:
-            _leave_bias_sink(y, ctx.gv[1], res)
+        planes = bool(planes_eligible(x.shape[-1], w.shape[-1]) and need[0] and need[1])
+        y = conv3x3_raw(x, w, _c(bias), _c(cbias), _c(res), xmax=xmax, planes=planes, wmax=wmax)
+        if planes:
+            y, x = y
+        gvb = _gv(bias)
+        conv = _ConvBwd(saved=(x, w), planes=planes, xmax=xmax, wmax=wmax, has=_has(bias, cbias, res), gv=(_gv(w), gvb),
+                        need=tuple(need[:5]))
+        ctx.save_for_backward(*conv.saved)
+        ctx.conv = conv._replace(saved=())
+        if gvb is not None and need[2]:
+            _leave_bias_sink(y, gvb, res)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        return _conv3x3_backward(ctx, dy)
+        return _conv3x3_backward(ctx.conv._replace(saved=ctx.saved_tensors), dy)
 
 
 def _leave_bias_sink(y, gvb, res):
@@ -660,18 +687,13 @@ def _bias_sink_of(x1, C1):
     return bs if (bs is not None and bs[0].numel() == C1) else None
 
 
-def _conv3x3_backward(ctx, dy):
-    """backward of y = conv3x3(x, w) + bias + cbias + res -> (dx, dw, dbias, dcbias, dres); ctx: the Conv3x3Fn context
-    or the stand-in GnConv3x3Fn builds (saved_tensors = (x or its planes, w), planes, xmax, wmax, has, gv,
-    needs_input_grad[0..4])"""
-    x, w = ctx.saved_tensors
-    has_bias, cb_dim, has_res = ctx.has
-    gvw, gvb = ctx.gv
+def _conv3x3_backward(rec, dy):
+    """backward of y = conv3x3(x, w) + bias + cbias + res -> (dx, dw, dbias, dcbias, dres); rec: the _ConvBwd of
+    Conv3x3Fn or GnConv3x3Fn"""
+    (x, w), x_is_planes, xmax, wmax, (has_bias, cb_dim, has_res), (gvw, gvb), need, want_max = rec
     B, N = dy.shape[0], dy.shape[-1]
-    want_max = bool(getattr(ctx, "want_dx_max", False))
 
     def wgrad_from_planes(dys, dymax):
-        xmax = ctx.xmax
         return _wgrad_to_sink(gvw, lambda out: conv3x3_wgrad_planes_raw(x, xmax, dys, dymax, B, w.shape[2], N, out=out),
                               (x, xmax, dys, dymax))
 
@@ -683,8 +705,8 @@ def _conv3x3_backward(ctx, dy):
         # may read dy's numbers (the tensor is a NaN stand-in).
         assert not has_res and cb_dim != 3 and _left(dy, "_colsum") is not None, "planes-only gradient misrouted"
         dys, dymax = gp
-        dx = conv3x3_dgrad_planes_raw(dys, dymax, w, wmax=ctx.wmax, want_max=want_max)
-        dw = wgrad_from_planes(dys, dymax) if ctx.needs_input_grad[1] else None
+        dx = conv3x3_dgrad_planes_raw(dys, dymax, w, wmax=wmax, want_max=want_max)
+        dw = wgrad_from_planes(dys, dymax) if need[1] else None
     else:
         nan = _NAN.get(dy.device)
         if nan is not None and dy.numel() > 1 and dy.data_ptr() == nan.data_ptr() and all(s == 0 for s in dy.stride()):
@@ -694,16 +716,14 @@ def _conv3x3_backward(ctx, dy):
                                "on the output of a ResnetBlock's conv1 are not supported with MULAN_GRAD_PLANES=1")
         dy = _c(dy)
         dymax = cached_absmax(dy) if (CONV_MODE == "f16x3" and N % 4 == 0) else None   # shared by dgrad and wgrad
-        if ctx.planes:                  # x is the plane tensor here
-            dx, dys = conv3x3_dgrad_raw(dy, w, dymax=dymax, planes=True, wmax=ctx.wmax, want_max=want_max)
+        if x_is_planes:                  # x is the plane tensor here
+            dx, dys = conv3x3_dgrad_raw(dy, w, dymax=dymax, planes=True, wmax=wmax, want_max=want_max)
             _leave(dy, "_planes", dys, dymax)   # the shortcut layer that shares this dy takes its weight gradient from them
             dw = wgrad_from_planes(dys, dymax)
         else:
-            dx = (conv3x3_dgrad_raw(dy, w, dymax=dymax, wmax=ctx.wmax, want_max=want_max)
-                  if ctx.needs_input_grad[0] else None)
+            dx = conv3x3_dgrad_raw(dy, w, dymax=dymax, wmax=wmax, want_max=want_max) if need[0] else None
             dw = None
-            if ctx.needs_input_grad[1]:   # written straight into the flat gradient buffer when the weight is a leaf
-                xmax = ctx.xmax
+            if need[1]:   # written straight into the flat gradient buffer when the weight is a leaf
                 dw = _wgrad_to_sink(gvw, lambda out: conv3x3_wgrad_raw(x, dy, out=out, xmax=xmax, dymax=dymax),
                                     (x, dy, xmax, dymax), ok=dymax is None or xmax is not None)
     dbias = dcb = None
@@ -711,13 +731,13 @@ def _conv3x3_backward(ctx, dy):
     parts = _left(dy, "_colsum_parts")                 # left by TeeFn.backward's add: 16 partial column sums per image
     if parts is not None and parts.shape[1] != N:
         parts = None
-    if parts is not None and has_bias and ctx.needs_input_grad[2] and not (cb_dim == 2 and ctx.needs_input_grad[3]):
+    if parts is not None and has_bias and need[2] and not (cb_dim == 2 and need[3]):
         dbias = colsum_raw(parts, 1, parts.shape[0], N, out=_fresh(gvb).view(1, N) if gvb is not None else None).view(N)
         _leave(dy, "_biasgrad", dbias.view(N), None)
-    elif (has_bias and ctx.needs_input_grad[2]) or (cb_dim == 2 and ctx.needs_input_grad[3]):
+    elif (has_bias and need[2]) or (cb_dim == 2 and need[3]):
         cs = _left(dy, "_colsum")                      # left by the GroupNorm backward that produced dy
         per_sample = cs if (cs is not None and cs.shape == (B, N)) else colsum_raw(dy, B, HW, N)    # [B,N]
-    if dbias is None and has_bias and ctx.needs_input_grad[2]:
+    if dbias is None and has_bias and need[2]:
         done = _left(dy, "_biasdone")                  # the GroupNorm backward already summed it into the sink
         twin = None
         if done is not None and gvb is not None and done[0].data_ptr() == gvb.data_ptr():
@@ -728,22 +748,15 @@ def _conv3x3_backward(ctx, dy):
         # the shortcut layer that shares this dy (nin_shortcut + bias) needs the very same column sum; twin: the sink it
         # was written into as well (a separate view: autograd adopts `dbias` itself)
         _leave(dy, "_biasgrad", dbias.view(N), twin)
-    if cb_dim is not None and ctx.needs_input_grad[3]:
+    if cb_dim is not None and need[3]:
         dcb = per_sample if cb_dim == 2 else dy
-    dres = dy if (has_res and ctx.needs_input_grad[4]) else None
+    dres = dy if (has_res and need[4]) else None
     assert gp is None or (dres is None and dcb is not dy)
     return dx, dw, dbias, dcb, dres
 
 
 def conv3x3(x, w, bias=None, cbias=None, res=None):
     return Conv3x3Fn.apply(x, w, bias, cbias, res)
-
-
-class _Ctx:
-    """a plain attribute bag standing in for an autograd context (see GnConv3x3Fn.backward)"""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 # ----------------------------------------------------------------------------- dense
@@ -786,7 +799,7 @@ def linear_pack(w, transpose, wmax=None):
     return wp, wmax
 
 
-def linear_f16x3_raw(x1, x2, wp, wmax, N1, N2, bias=None, res=None, planes=False):
+def linear_f16x3_raw(x1, x2, wp, wmax, N1, N2, *, bias=None, res=None, planes=False):
     """[x1 | x2] @ W + bias + res -> (y1 [B,1024,N1], y2 [B,1024,N2] or None); x* are [B,1024,K*] pixel tensors.
     planes=True: also returns (xs, xmax): the split planes of [x1 | x2] and the per-image maxima they were scaled with
     (the input of linear_wgrad_planes_raw)."""
@@ -813,7 +826,7 @@ def linear_wgrad_planes_raw(xs, xmax, dys, dymax, B, K, N, out=None):
                          (ptr(xs), ptr(xmax), ptr(dys), ptr(dymax)), B, K, N, 1, out, xs.device, _share_chip())
 
 
-def linear_wgrad_x32_raw(x1, x2, xmax, xmax2, dys, dymax, B, N, out=None):
+def linear_wgrad_x32_raw(x1, x2, xmax, xmax2, dys, dymax, B, N, *, out=None):
     """dw[K1 + K2, N] = [x1 | x2]^T dy with x in fp32 (split while staged: the kernel is memory bound) and dy as the
     planes handed on by the convolution that consumed the same dy; xmax / xmax2 = the maxima of x1 / x2 (the kernel
     scales the concat with their elementwise max, as the forward kernel did: no separate launch for it).  Bit-identical to
@@ -827,7 +840,7 @@ def linear_wgrad_x32_raw(x1, x2, xmax, xmax2, dys, dymax, B, N, out=None):
 
 # the dense weight gradient reads the layer's fp32 input and splits it in its staging path (round 3) instead of taking
 # planes the forward kernel wrote as a by-product; A/B switch: 0 = the round-2 plane hand-over
-LINEAR_WGRAD_X32 = _os.environ.get("MULAN_LINEAR_WGRAD_X32", "1") == "1"
+LINEAR_WGRAD_X32 = _flag("LINEAR_WGRAD_X32", "1")
 
 
 class LinearFn(torch.autograd.Function):
@@ -947,7 +960,7 @@ class CondProjGroup:
         return self._outs
 
 
-GROUP_COND_PROJ = _os.environ.get("MULAN_GROUP_COND_PROJ", "1") == "1"
+GROUP_COND_PROJ = _flag("GROUP_COND_PROJ", "1")
 
 
 def cond_proj(cond, w):
@@ -971,18 +984,18 @@ class Linear2Fn(torch.autograd.Function):
         M = a1.shape[0]
         ctx.fast = linear_fast_ok(x1, K1, K2, N, 0) and K1 % 128 == 0 and K2 % 128 == 0
         ctx.wmax = None
-        ctx.xs = None
+        # what the weight gradient takes its x operand from: x32 = the maxima of (x1, x2), the kernel splits the fp32
+        # inputs itself; xs / xsmax = the planes the forward kernel wrote and their maxima; neither: the fp32 GEMM
+        ctx.x32 = ctx.xs = ctx.xsmax = None
         if ctx.fast:      # one pass over both inputs, no intermediate
             wp, ctx.wmax = linear_pack(w, False)
-            ctx.x32 = None
-            if ctx.needs_input_grad[2] and LINEAR_WGRAD_X32 and K1 % 128 == 0 and K2 % 128 == 0 and N % 128 == 0:
-                y = linear_f16x3_raw(x1, x2, wp, ctx.wmax, N, 0, bias=_c(bias))[0].view(M, N)
+            want_xs = bool(ctx.needs_input_grad[2] and not LINEAR_WGRAD_X32)    # (fast: K1, K2, N are 128-multiples)
+            out = linear_f16x3_raw(x1, x2, wp, ctx.wmax, N, 0, bias=_c(bias), planes=want_xs)
+            y = out[0].view(M, N)
+            if want_xs:
+                ctx.xs, ctx.xsmax = out[2:]
+            elif ctx.needs_input_grad[2]:
                 ctx.x32 = (cached_absmax(x1), cached_absmax(x2))      # the maxima the forward kernel just used: [B, 16] each
-            elif ctx.needs_input_grad[2] and (K1 + K2) % 128 == 0 and N % 128 == 0:
-                y, _, ctx.xs, ctx.xsmax = linear_f16x3_raw(x1, x2, wp, ctx.wmax, N, 0, bias=_c(bias), planes=True)
-                y = y.view(M, N)
-            else:
-                y = linear_f16x3_raw(x1, x2, wp, ctx.wmax, N, 0, bias=_c(bias))[0].view(M, N)
         else:
             y = gemm_raw(a1, w[:K1], M, N, K1, bias=_c(bias))
             y = gemm_raw(a2, w[K1:], M, N, K2, R=y, out=torch.empty_like(y))
@@ -1012,7 +1025,7 @@ class Linear2Fn(torch.autograd.Function):
         gvw, gvb = ctx.gv
         if ctx.needs_input_grad[2]:
             pl = _left(dy, "_planes")       # (planes of dy, its maxima) left by the convolution that consumed the same dy
-            x32 = getattr(ctx, "x32", None)
+            x32 = ctx.x32
             if x32 is not None and pl is not None and pl[0].numel() == M * N * 4:
                 B_ = M // HW
                 x1v, x2v = a1.view(B_, HW, K1), a2.view(B_, HW, K2)
@@ -1079,7 +1092,7 @@ def _seed_args(seed):
     return int(seed), None
 
 
-GN_FUSED_REDUCE = _os.environ.get("MULAN_GN_FUSED_REDUCE", "1") == "1"   # A/B switch: 0 = separate mulan_colsum launches
+GN_FUSED_REDUCE = _flag("GN_FUSED_REDUCE", "1")   # A/B switch: 0 = separate mulan_colsum launches
 _TICKETS = {}
 
 
@@ -1100,7 +1113,28 @@ def reset_tickets():
         t.zero_()
 
 
-def _gn_forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset):
+class _GnBwd(NamedTuple):
+    """what _gn_backward reads.  GroupNormFn, GroupNormSkipFn (_gn_forward) and GnConv3x3Fn build it in forward; `saved`
+    goes through save_for_backward and is put back at the top of backward, as in _ConvBwd."""
+    saved: tuple                   # (x1, x2 or None, gamma, beta, mean, rstd)
+    meta: tuple                    # (groups, act, keep, seed: int or 1-element device tensor, offset)
+    gv: tuple                      # (_gv(gamma), _gv(beta)): the gradient sinks
+    bias_sink: Optional[tuple]     # _bias_sink_of(x1): the bias sinks of the convolution that produced x1
+    keepbits: Optional[torch.Tensor] = None    # the dropout keep-bits the forward kernel stored; None: drawn again
+
+
+def gn_reduce_grid_ok(C1, C2, groups):
+    """the channel grid of the GroupNorm kernels that reduce over the samples inside the launch
+    (mulan_groupnorm_bwd_fused, _fused_planes) and write planes (GnConv3x3Fn): both inputs in 32-channel slices, one
+    maxima slot per slice, groups of 4 ... 32 channels that do not straddle a slice"""
+    Ct = C1 + C2
+    cpg = Ct // groups
+    return C1 % 32 == 0 and C2 % 32 == 0 and Ct // 32 <= MAX_PARTS and cpg % 4 == 0 and 32 % cpg == 0
+
+
+def _gn_forward(ctx, x1, x2, gamma, beta, norm):
+    """norm = (groups, eps, act, keep, seed, offset)"""
+    groups, eps, act, keep, seed, offset = norm
     x1, x2 = _c(x1), _c(x2)
     B, C1 = x1.shape[0], x1.shape[-1]
     C2 = 0 if x2 is None else x2.shape[-1]
@@ -1113,72 +1147,61 @@ def _gn_forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset):
     call("mulan_groupnorm_fwd_dyn", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), B,
          HW, groups, float(eps), int(act), float(keep), sv, int(offset), ptr(sd), ptr(ymax), stream())
     _leave_maxima(y, ymax)
-    ctx.save_for_backward(x1, x2, gamma, beta, mean, rstd)
-    ctx.meta = (groups, int(act), float(keep), seed, int(offset))
-    ctx.gv = (_gv(gamma), _gv(beta))
-    ctx.bias_sink = _bias_sink_of(x1, C1)
+    gn = _GnBwd(saved=(x1, x2, gamma, beta, mean, rstd), meta=(groups, int(act), float(keep), seed, int(offset)),
+                gv=(_gv(gamma), _gv(beta)), bias_sink=_bias_sink_of(x1, C1))
+    ctx.save_for_backward(*gn.saved)
+    ctx.gn = gn._replace(saved=())
     return y, x1, x2
 
 
-def _gn_backward(ctx, dy, add1=None, add2=None, planes_out=False, add1b=None):
-    """dx1, dx2 (+ the gradients add1 / add2 that reach x1 / x2 through a skip path), dgamma, dbeta.  The written dx1
-    carries its maxima and per-sample channel sums for the convolution in front (whose dy it is).
+def _gn_backward(rec, dy, add1=None, add2=None, planes_out=False, add1b=None):
+    """dx1, dx2 (+ the gradients add1 / add2 that reach x1 / x2 through a skip path), dgamma, dbeta; rec: the _GnBwd of
+    the node.  The written dx1 carries its maxima and per-sample channel sums for the convolution in front (whose dy it
+    is).
     planes_out: the caller vouches that dx1 is consumed ONLY by the f16x3 kernels of the convolution that produced x1
     (GnConv3x3Fn with x1_grad_planes): where the kernel variant applies (single input, no skip-path gradient, dy with
     its maxima) dx1 is then written as split planes and returned as a planes-only stand-in (_planes_only_grad)."""
-    x1, x2, gamma, beta, mean, rstd = ctx.saved_tensors
-    groups, act, keep, seed, offset = ctx.meta
+    x1, x2, gamma, beta, mean, rstd = rec.saved
+    groups, act, keep, seed, offset = rec.meta
     dy = _c(dy)
+    dev = dy.device
     B, C1 = x1.shape[0], x1.shape[-1]
     C2 = 0 if x2 is None else x2.shape[-1]
     Ct = C1 + C2
     dymax_in = _left(dy, "_absmax")
     if add1b is not None and add1 is None:
         add1, add1b = add1b, None
-    if (planes_out and GN_FUSED_REDUCE and x2 is None and add1 is None and dymax_in is not None and
-            C1 % 32 == 0 and C1 // 32 <= 16 and (C1 // groups) % 4 == 0 and
-            32 % (C1 // groups) == 0 and B * HW * C1 * 4 < 2 ** 31):
-        dxp = torch.empty(B * HW * C1 * 4, device=dy.device, dtype=torch.uint8)
-        bound = torch.empty((B, MAX_PARTS), device=dy.device, dtype=torch.int32)
-        parts = torch.empty((2, B, C1), device=dy.device, dtype=torch.float32)
-        csum = torch.empty((B, C1), device=dy.device, dtype=torch.float32)
-        sv, sd = _seed_args(seed)
-        gvg, gvb = ctx.gv
-        dgamma = _fresh(gvg) if gvg is not None else torch.empty(C1, device=dy.device, dtype=torch.float32)
-        dbeta = _fresh(gvb) if gvb is not None else torch.empty(C1, device=dy.device, dtype=torch.float32)
-        sink, sink2 = ctx.bias_sink if ctx.bias_sink is not None else (None, None)
-        call("mulan_groupnorm_bwd_fused_planes", ptr(dy), ptr(dymax_in), ptr(x1), C1, ptr(gamma), ptr(beta), ptr(mean),
-             ptr(rstd), ptr(dxp), ptr(parts[0]), ptr(parts[1]), B, HW, groups, act, keep, sv, offset, ptr(sd), ptr(bound),
-             ptr(csum), ptr(dgamma), ptr(dbeta), ptr(sink), ptr(sink2), ptr(_gn_tickets(dy.device)),
-             ptr(getattr(ctx, "keepbits", None)), stream())
-        dx1 = _planes_only_grad(x1.shape, dy.device, dxp, bound)
-        if sink is not None:
-            _leave(dx1, "_biasdone", sink, sink2)
-        _leave(dx1, "_colsum", csum)
-        return dx1, None, dgamma, dbeta
-    dx1 = torch.empty_like(x1)
-    dx2 = torch.empty_like(x2) if x2 is not None else None
-    parts = torch.empty((2, B, Ct), device=dy.device, dtype=torch.float32)     # dgamma / dbeta per-sample partials
-    dgp, dbp = parts[0], parts[1]
-    f16 = CONV_MODE == "f16x3"
-    m1 = torch.empty((B, MAX_PARTS), device=dy.device, dtype=torch.int32) if f16 and C1 // 32 <= MAX_PARTS else None
-    m2 = (torch.empty((B, MAX_PARTS), device=dy.device, dtype=torch.int32)
-          if f16 and x2 is not None and C2 // 32 <= MAX_PARTS else None)
-    csum = torch.empty((B, Ct), device=dy.device, dtype=torch.float32)
     sv, sd = _seed_args(seed)
-    gvg, gvb = ctx.gv
-    dgamma = _fresh(gvg) if gvg is not None else torch.empty(Ct, device=dy.device, dtype=torch.float32)
-    dbeta = _fresh(gvb) if gvb is not None else torch.empty(Ct, device=dy.device, dtype=torch.float32)
-    cpg = Ct // groups
-    fused = (GN_FUSED_REDUCE and C1 % 32 == 0 and C2 % 32 == 0 and Ct // 32 <= 16 and cpg % 4 == 0 and 32 % cpg == 0)
-    if fused:         # the sums over the samples (dgamma, dbeta, the bias gradient of the convolution in front) in-kernel
-        sink, sink2 = ctx.bias_sink if ctx.bias_sink is not None else (None, None)
+    gvg, gvb = rec.gv
+    sink, sink2 = rec.bias_sink if rec.bias_sink is not None else (None, None)
+    # the sums over the samples (dgamma, dbeta, the bias gradient of the convolution in front) inside the launch
+    fused = GN_FUSED_REDUCE and gn_reduce_grid_ok(C1, C2, groups)
+    planes = bool(planes_out and fused and x2 is None and add1 is None and dymax_in is not None and
+                  B * HW * C1 * 4 < 2 ** 31)
+    if planes:
+        dxp = torch.empty(B * HW * C1 * 4, device=dev, dtype=torch.uint8)
+        bound = torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32)
+    else:
+        dx1 = torch.empty_like(x1)
+        dx2 = torch.empty_like(x2) if x2 is not None else None
+    parts = torch.empty((2, B, Ct), device=dev, dtype=torch.float32)     # dgamma / dbeta per-sample partials
+    dgp, dbp = parts[0], parts[1]
+    f16 = CONV_MODE == "f16x3" and not planes          # (the plane variant leaves the maxima of dx1 in `bound`)
+    m1 = _maxima_slots(B, C1 // 32, dev, f16)
+    m2 = _maxima_slots(B, C2 // 32, dev, f16 and x2 is not None)
+    csum = torch.empty((B, Ct), device=dev, dtype=torch.float32)
+    dgamma = _fresh(gvg) if gvg is not None else torch.empty(Ct, device=dev, dtype=torch.float32)
+    dbeta = _fresh(gvb) if gvb is not None else torch.empty(Ct, device=dev, dtype=torch.float32)
+    if planes:
+        call("mulan_groupnorm_bwd_fused_planes", ptr(dy), ptr(dymax_in), ptr(x1), C1, ptr(gamma), ptr(beta), ptr(mean),
+             ptr(rstd), ptr(dxp), ptr(dgp), ptr(dbp), B, HW, groups, act, keep, sv, offset, ptr(sd), ptr(bound),
+             ptr(csum), ptr(dgamma), ptr(dbeta), ptr(sink), ptr(sink2), ptr(_gn_tickets(dev)), ptr(rec.keepbits), stream())
+        dx1, dx2 = _planes_only_grad(x1.shape, dev, dxp, bound), None
+    elif fused:
         call("mulan_groupnorm_bwd_fused", ptr(dy), ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
              ptr(dx1), ptr(dx2), ptr(dgp), ptr(dbp), B, HW, groups, act, keep, sv, offset, ptr(sd), ptr(m1), ptr(m2),
              ptr(_c(add1)), ptr(_c(add2)), ptr(_c(add1b)), ptr(csum), ptr(dgamma), ptr(dbeta), ptr(sink), ptr(sink2),
-             ptr(_gn_tickets(dy.device)), stream())
-        if sink is not None:
-            _leave(dx1, "_biasdone", sink, sink2)
+             ptr(_gn_tickets(dev)), stream())
     else:
         if add1b is not None:
             add1 = add1 + add1b
@@ -1190,6 +1213,8 @@ def _gn_backward(ctx, dy, add1=None, add2=None, planes_out=False, add1b=None):
         else:
             colsum_raw(dgp, 1, B, Ct, out=dgamma.view(1, Ct))
             colsum_raw(dbp, 1, B, Ct, out=dbeta.view(1, Ct))
+    if fused and sink is not None:
+        _leave(dx1, "_biasdone", sink, sink2)
     if m1 is not None:
         _leave(dx1, "_absmax", m1)
     if m2 is not None:
@@ -1203,22 +1228,21 @@ class GroupNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset):
-        return _gn_forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset)[0]
+        return _gn_forward(ctx, x1, x2, gamma, beta, (groups, eps, act, keep, seed, offset))[0]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        return _gn_backward(ctx, dy) + (None,) * 6
+        return _gn_backward(ctx.gn._replace(saved=ctx.saved_tensors), dy) + (None,) * 6
 
 
-def _skip_outputs(ctx, y, x1, x2, tagged=None):
+def _skip_outputs(y, x1, x2, tagged=None):
     """(y, s1) or (y, s1, s2): y with the aliases of x1 (, x2) for the block's skip path.  The maxima a producer left on
     x (on `tagged`, where x1 / x2 are contiguous copies of what the caller was given) stay valid for the alias."""
     t1, t2 = (x1, x2) if tagged is None else tagged
     s1 = _carry(t1, x1.view_as(x1), tags=("_absmax",))
     s2 = _carry(t2, x2.view_as(x2), tags=("_absmax",)) if x2 is not None else None
-    ctx.has2 = x2 is not None
-    return (y, s1, s2) if ctx.has2 else (y, s1)
+    return (y, s1) if x2 is None else (y, s1, s2)
 
 
 class GroupNormSkipFn(torch.autograd.Function):
@@ -1228,15 +1252,15 @@ class GroupNormSkipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset):
-        y, x1c, x2c = _gn_forward(ctx, x1, x2, gamma, beta, groups, eps, act, keep, seed, offset)
-        return _skip_outputs(ctx, y, x1c, x2c, tagged=(x1, x2))
+        y, x1c, x2c = _gn_forward(ctx, x1, x2, gamma, beta, (groups, eps, act, keep, seed, offset))
+        return _skip_outputs(y, x1c, x2c, tagged=(x1, x2))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy, ds1, ds2=None):
         if dy is None:     # only the skip path was used downstream
             return (ds1, ds2) + (None,) * 8
-        return _gn_backward(ctx, dy, ds1, ds2) + (None,) * 6
+        return _gn_backward(ctx.gn._replace(saved=ctx.saved_tensors), dy, ds1, ds2) + (None,) * 6
 
 
 def group_norm(x1, x2, gamma, beta, *, groups=32, eps=1e-6, act=True, keep=1.0, seed=0, offset=0):
@@ -1249,13 +1273,13 @@ def group_norm_skip(x1, x2, gamma, beta, *, groups=32, eps=1e-6, act=True, keep=
     return out if len(out) == 3 else (out[0], out[1], None)
 
 
-GN_CONV_PLANES = _os.environ.get("MULAN_GN_CONV_PLANES", "1") == "1"    # A/B switch: 0 = fp32 hand-over (two ops)
+GN_CONV_PLANES = _flag("GN_CONV_PLANES", "1")    # A/B switch: 0 = fp32 hand-over (two ops)
 # Backward counterpart (round 3): the gradient a GroupNorm backward hands to the convolution in front of it (norm2 ->
 # conv1 of a ResnetBlock) goes as split planes too -- the input-gradient convolution then runs on the plane-fed
 # instantiation of the kernel (no split, no plane stores out of the MFMA kernel).  A/B switch: 0 = fp32 hand-over.
-GRAD_PLANES = _os.environ.get("MULAN_GRAD_PLANES", "1") == "1"
+GRAD_PLANES = _flag("GRAD_PLANES", "1")
 # the dropout keep-bits of norm2 are stored by the forward kernel and re-used by the backward kernel (A/B: 0 = re-drawn)
-KEEP_BITS = _os.environ.get("MULAN_KEEP_BITS", "1") == "1"
+KEEP_BITS = _flag("KEEP_BITS", "1")
 # GroupNorm normalised inside the convolution's patch fill (mulan_groupnorm_stats + mulan_conv3x3_fwd_f16x3_gn_in) where no
 # dropout is drawn.  GN_FILL: wherever the convolution's weight needs no gradient (evaluators, sampler, the ODE
 # evaluator's input-only differentiation) and the convolution has one 128-wide block of output channels: the normalised
@@ -1264,21 +1288,21 @@ KEEP_BITS = _os.environ.get("MULAN_KEEP_BITS", "1") == "1"
 # evaluation at E = 256: +4.5 %), so those layers keep the plane hand-over; GN_FILL_MAX_N is that limit.
 # GN_FILL_TRAIN (A/B switch, off: the train step is 1.2 % slower with it, profiles/DESIGN_r04.md 3.2): also in training, the convolution
 # then stores the planes for its weight gradient.
-GN_FILL = _os.environ.get("MULAN_GN_FILL", "1") == "1"
+GN_FILL = _flag("GN_FILL", "1")
 GN_FILL_MAX_N = int(_os.environ.get("MULAN_GN_FILL_MAX_N", "128"))
-GN_FILL_TRAIN = _os.environ.get("MULAN_GN_FILL_TRAIN", "0") == "1"
+GN_FILL_TRAIN = _flag("GN_FILL_TRAIN", "0")
 # ... and the statistics handed from convolution to convolution: a GroupNorm-fed convolution leaves the partial sums of
 # its output (per image, 8-row tile, channel quad) on the tensor, the next one forms mean / rstd from them in its prologue:
 # no pass over the tensor between two convolutions of a forward-only chain.  A/B switch: 0 = mulan_groupnorm_stats in
 # front of every convolution (bit-identical to the plane hand-over; with the hand-over the statistics agree to rounding).
-GN_FILL_STATS = _os.environ.get("MULAN_GN_FILL_STATS", "1") == "1"
+GN_FILL_STATS = _flag("GN_FILL_STATS", "1")
 # training step: GroupNorm forward as the streaming kernel on the statistics the producing convolution left, where that
 # kernel is the faster one (GnConv3x3Fn.forward): dropout layers and the 2 x 128-channel concat, at 32 <= images per launch
 # <= 96 -- the per-GPU batches of an 8-GPU job.  Measured in the train step of BASELINE configs[2]
 # (profiles/r05_gn_fwd_stream_in_step.log): 64 images 42.78 -> 42.50 ms, 32 images 28.52 -> 28.42, 16 images 23.42 -> 23.65,
 # 128 images 78.98 -> 79.08 (what the kernel gains alone, 4 us per launch, the statistics in the convolution epilogue cost
 # back).  MULAN_GN_FWD_STREAM=0: the slab kernel everywhere (the round-4 path); GN_FWD_STREAM_B: the batch window.
-GN_FWD_STREAM = _os.environ.get("MULAN_GN_FWD_STREAM", "1") == "1"
+GN_FWD_STREAM = _flag("GN_FWD_STREAM", "1")
 GN_FWD_STREAM_B = tuple(int(v) for v in _os.environ.get("MULAN_GN_FWD_STREAM_B", "32,96").split(","))
 
 
@@ -1311,21 +1335,65 @@ def _conv_outputs(B, N, dev, bias, cbias, res, want_stats):
     one row of partial sums per row tile of that launch (8, 4 or 2 image rows) for the GroupNorm behind it"""
     y = torch.empty((B, HW, N), device=dev, dtype=torch.float32)
     ymax = _maxima_slots(B, (H // 8) * (N // 128), dev)
-    mode = 0 if cbias is None else (1 if cbias.dim() == 2 else 2)
     bias_c, cb_c, res_c = _c(bias), _c(cbias), _c(res)
     ystats = None
     if want_stats:
         rows = lib.load().mulan_conv3x3_f16x3_tile_rows(B, H, N, int(ymax is not None))
         ystats = torch.empty((B, H // rows, N // 4, 2), device=dev, dtype=torch.float32)
-    return y, ymax, mode, bias_c, cb_c, res_c, ystats
+    return y, ymax, _cbias_mode(cbias), bias_c, cb_c, res_c, ystats
 
 
 def gn_conv_ok(C1, C2, N, groups):
     """GroupNorm -> 3x3 convolution with the normalised tensor handed over as split fp16 planes (GnConv3x3Fn)"""
     Ct = C1 + C2
-    cpg = Ct // groups
-    return (GN_CONV_PLANES and CONV_MODE == "f16x3" and Ct % 128 == 0 and N % 128 == 0 and Ct // 32 <= MAX_PARTS and
-            C1 % 32 == 0 and C2 % 32 == 0 and Ct % groups == 0 and cpg % 4 == 0 and 32 % cpg == 0)
+    return (GN_CONV_PLANES and CONV_MODE == "f16x3" and Ct % 128 == 0 and N % 128 == 0 and Ct % groups == 0 and
+            gn_reduce_grid_ok(C1, C2, groups))
+
+
+def _gn_conv_norm(x1, x2, gamma, beta, norm, fill, want_planes, want_bits):
+    """The GroupNorm stage of GnConv3x3Fn.forward; norm = (groups, eps, act, keep, seed, offset).  Returns what the
+    convolution stage and the backward pass need: (ys, bound, mean, rstd, keepbits, st1, st2).
+    fill: only the statistics here (mulan_groupnorm_stats -- or none at all: st1 / st2, the partial sums the producing
+    convolutions left, go to the convolution, which normalises inside its patch fill); ys is then the plane tensor that
+    convolution writes for its weight gradient (want_planes; else empty).
+    Otherwise ys = the normalised tensor as split planes scaled with `bound`, and keepbits (want_bits) the dropout bits as
+    drawn."""
+    groups, eps, act, keep, seed, offset = norm
+    B, C1 = x1.shape[0], x1.shape[-1]
+    C2 = 0 if x2 is None else x2.shape[-1]
+    Ct, dev = C1 + C2, x1.device
+    bound = torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32)
+    mean = torch.empty((B, groups), device=dev, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    gn_in = (ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta))
+    if fill:
+        st1, st2 = _gn_stats_pair(x1, x2, C1, C2) if GN_FILL_STATS and not want_planes else (None, None)
+        if st1 is None:
+            call("mulan_groupnorm_stats", *gn_in, ptr(mean), ptr(rstd), ptr(bound), B, HW, groups, eps, stream())
+        ys = torch.empty(B * HW * Ct * 4 if want_planes else 0, device=dev, dtype=torch.uint8)
+        return ys, bound, mean, rstd, None, st1, st2
+    ys = torch.empty(B * HW * Ct * 4, device=dev, dtype=torch.uint8)
+    sv, sd = _seed_args(seed)
+    # the convolutions that produced x1 (, x2) left the partial sums of the statistics: the streaming kernel (no
+    # statistics phase, 62 registers) where it is the faster one -- dropout layers and the 2 x 128-channel concat
+    # (profiles/r05_gn_stream_bench.log: 31.8 vs 36.0 us and 52.4 vs 55.6 us at B = 128; 128 channels without
+    # dropout: 30.2 vs 27.7 us, the slab kernel stays), see GN_FWD_STREAM
+    st1 = st2 = None
+    if _gn_fwd_stream_on(B) and (keep < 1.0 or C2 > 0) and Ct // 32 <= MAX_PARTS:
+        st1, st2 = _gn_stats_pair(x1, x2, C1, C2)
+    # dropout layer whose backward will write planes (x1_grad_planes): keep the 4 keep-bits per float4 as drawn (2 MB at
+    # B = 128, C = 128), so that the backward kernel does not repeat the Philox rounds
+    keepbits = torch.empty(B * (Ct // 32) * 1024, device=dev, dtype=torch.int32) if want_bits else None
+    out = (ptr(ys), ptr(mean), ptr(rstd))
+    tail = (B, HW, groups, eps, act, keep, sv, offset, ptr(sd), ptr(bound))
+    if st1 is not None:
+        call("mulan_groupnorm_fwd_stream", *gn_in, None, *out, ptr(st1), ptr(st2), int(st1.shape[1]), *tail, ptr(keepbits),
+             stream())
+    elif want_bits:
+        call("mulan_groupnorm_fwd_planes_keepbits", *gn_in, *out, *tail, ptr(keepbits), stream())
+    else:
+        call("mulan_groupnorm_fwd_planes", *gn_in, *out, *tail, stream())
+    return ys, bound, mean, rstd, keepbits, None, None
 
 
 class GnConv3x3Fn(torch.autograd.Function):
@@ -1340,6 +1408,7 @@ class GnConv3x3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, groups, eps, act, keep, seed, offset, skip,
                 x1_grad_planes=False):
+        need = ctx.needs_input_grad
         # x1_grad_planes: the caller vouches that x1 has no consumer besides this op (conv1's output inside a
         # ResnetBlock); if x1's producer accepts it (tag below), d x1 then travels as split planes only
         ctx.x1_grad_planes = bool(x1_grad_planes and not skip and x2 is None and _left(x1, "_accepts_grad_planes"))
@@ -1347,131 +1416,76 @@ class GnConv3x3Fn(torch.autograd.Function):
         # that arrives through that connection (it is there first: the up path runs first in the backward pass)
         box = getattr(x1, "_grad_box", None)
         ctx.grad_box = None
-        if box is not None and skip and not box.claimed and ctx.needs_input_grad[0]:
+        if box is not None and skip and not box.claimed and need[0]:
             box.claimed = True
             ctx.grad_box = box
         x1, x2, w = _c(x1), _c(x2), _c(w)
         B, C1 = x1.shape[0], x1.shape[-1]
         C2 = 0 if x2 is None else x2.shape[-1]
-        Ct, N = C1 + C2, w.shape[-1]
-        dev = x1.device
-        bound = torch.empty((B, MAX_PARTS), device=dev, dtype=torch.int32)
-        mean = torch.empty((B, groups), device=dev, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        fill = (float(keep) >= 1.0 and (C2 == 0 or C2 == C1) and Ct <= 512 and N <= GN_FILL_MAX_N and
-                (GN_FILL_TRAIN if ctx.needs_input_grad[4] else GN_FILL))
-        if fill:
-            return GnConv3x3Fn._forward_fill(ctx, x1, x2, gamma, beta, w, bias, cbias, res, groups, eps, act, skip, bound,
-                                             mean, rstd)
-        ys = torch.empty(B * HW * Ct * 4, device=dev, dtype=torch.uint8)
-        sv, sd = _seed_args(seed)
-        # dropout layer whose backward will write planes (x1_grad_planes): keep the 4 keep-bits per float4 as drawn (2 MB at
-        # B = 128, C = 128), so that the backward kernel does not repeat the Philox rounds
-        keepbits = None
-        want_bits = KEEP_BITS and float(keep) < 1.0 and ctx.x1_grad_planes and any(ctx.needs_input_grad[:5])
-        # the convolutions that produced x1 (, x2) left the partial sums of the statistics: the streaming kernel (no
-        # statistics phase, 62 registers) where it is the faster one -- dropout layers and the 2 x 128-channel concat
-        # (profiles/r05_gn_stream_bench.log: 31.8 vs 36.0 us and 52.4 vs 55.6 us at B = 128; 128 channels without
-        # dropout: 30.2 vs 27.7 us, the slab kernel stays), see GN_FWD_STREAM
-        st1 = st2 = None
-        if _gn_fwd_stream_on(B) and (float(keep) < 1.0 or C2 > 0) and Ct // 32 <= MAX_PARTS:
-            st1, st2 = _gn_stats_pair(x1, x2, C1, C2)
-        if st1 is not None:
-            if want_bits:
-                keepbits = torch.empty(B * (Ct // 32) * 1024, device=dev, dtype=torch.int32)
-            call("mulan_groupnorm_fwd_stream", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), None, ptr(ys), ptr(mean),
-                 ptr(rstd), ptr(st1), ptr(st2), int(st1.shape[1]), B, HW, groups, float(eps), int(act), float(keep), sv,
-                 int(offset), ptr(sd), ptr(bound), ptr(keepbits), stream())
-        elif want_bits:
-            keepbits = torch.empty(B * (Ct // 32) * 1024, device=dev, dtype=torch.int32)
-            call("mulan_groupnorm_fwd_planes_keepbits", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(ys), ptr(mean),
-                 ptr(rstd), B, HW, groups, float(eps), int(act), float(keep), sv, int(offset), ptr(sd), ptr(bound),
-                 ptr(keepbits), stream())
-        else:
-            call("mulan_groupnorm_fwd_planes", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(ys), ptr(mean), ptr(rstd),
-                 B, HW, groups, float(eps), int(act), float(keep), sv, int(offset), ptr(sd), ptr(bound), stream())
-        ctx.keepbits = keepbits
-        wp, wmax = _pack_weights(w, Ct, N, 0)
-        # ystats: by-product for the GroupNorm behind this convolution (see above)
-        y, ymax, mode, bias_c, cb_c, res_c, ystats = _conv_outputs(B, N, dev, bias, cbias, res,
-                                                                   _gn_fwd_stream_on(B) and N // 32 <= MAX_PARTS)
-        _timed("conv3x3_f16x3_kernel<planes_in>", 2.0 * B * HW * 9 * Ct * N,
-               lambda: call("mulan_conv3x3_fwd_f16x3_planes_in_stats", ptr(ys), ptr(bound), ptr(wp), ptr(wmax), ptr(bias_c),
-                            ptr(cb_c), mode, ptr(res_c), ptr(y), ptr(ymax), ptr(ystats), 1, B, H, W, Ct, N, stream()))
-        return GnConv3x3Fn._finish_forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, mean, rstd, ys, bound, wmax, y, ymax,
-                                           ystats, (groups, int(act), float(keep), seed, int(offset)), skip, mode)
-
-    @staticmethod
-    def _forward_fill(ctx, x1, x2, gamma, beta, w, bias, cbias, res, groups, eps, act, skip, bound, mean, rstd):
-        """statistics pass + the convolution that normalises inside its patch fill (no dropout): bit for bit the result of
-        the two-kernel path above"""
-        B, C1 = x1.shape[0], x1.shape[-1]
-        C2 = 0 if x2 is None else x2.shape[-1]
         Ct, N, dev = C1 + C2, w.shape[-1], x1.device
-        want_planes = bool(ctx.needs_input_grad[4])
-        st1, st2 = _gn_stats_pair(x1, x2, C1, C2) if GN_FILL_STATS and not want_planes else (None, None)
-        if st1 is None:
-            call("mulan_groupnorm_stats", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(bound), B,
-                 HW, groups, float(eps), stream())
-        ys = torch.empty(B * HW * Ct * 4 if want_planes else 0, device=dev, dtype=torch.uint8)
-        ctx.keepbits = None
+        eps, act, keep, offset = float(eps), int(act), float(keep), int(offset)
+        # fill: statistics pass + the convolution that normalises inside its patch fill (no dropout): bit for bit the
+        # result of the two-kernel path
+        fill = (keep >= 1.0 and (C2 == 0 or C2 == C1) and Ct <= 512 and N <= GN_FILL_MAX_N and
+                (GN_FILL_TRAIN if need[4] else GN_FILL))
+        want_planes = bool(need[4])      # (the weight gradient reads them)
+        want_bits = bool(KEEP_BITS and keep < 1.0 and ctx.x1_grad_planes and any(need[:5]))
+        ys, bound, mean, rstd, keepbits, st1, st2 = _gn_conv_norm(x1, x2, gamma, beta, (groups, eps, act, keep, seed, offset),
+                                                                  fill, want_planes, want_bits)
         wp, wmax = _pack_weights(w, Ct, N, 0)
-        y, ymax, mode, bias_c, cb_c, res_c, ystats = _conv_outputs(B, N, dev, bias, cbias, res,
-                                                                   GN_FILL_STATS and not want_planes)
-        _timed("conv3x3_f16x3_kernel<gn_in>", 2.0 * B * HW * 9 * Ct * N,
-               lambda: call("mulan_conv3x3_fwd_f16x3_gn_in", ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(mean),
-                            ptr(rstd), groups, int(act), float(eps), ptr(bound), ptr(st1), ptr(st2),
-                            0 if st1 is None else int(st1.shape[1]), ptr(wp), ptr(wmax),
-                            ptr(bias_c), ptr(cb_c), mode, ptr(res_c), ptr(y), ptr(ymax), ptr(ystats),
-                            ptr(ys) if want_planes else None, B, H, W, N, stream()))
-        return GnConv3x3Fn._finish_forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, mean, rstd, ys, bound, wmax, y, ymax,
-                                           ystats, (groups, int(act), 1.0, 0, 0), skip, mode)
-
-    @staticmethod
-    def _finish_forward(ctx, x1, x2, gamma, beta, w, bias, cbias, res, mean, rstd, ys, bound, wmax, y, ymax, ystats, meta,
-                        skip, mode):
-        B, C1 = x1.shape[0], x1.shape[-1]
-        Ct, N = C1 + (0 if x2 is None else x2.shape[-1]), w.shape[-1]
+        # ystats: by-product for the GroupNorm behind this convolution (GN_FILL_STATS, GN_FWD_STREAM)
+        want_stats = (GN_FILL_STATS and not want_planes) if fill else (_gn_fwd_stream_on(B) and N // 32 <= MAX_PARTS)
+        y, ymax, mode, bias_c, cb_c, res_c, ystats = _conv_outputs(B, N, dev, bias, cbias, res, want_stats)
+        epilogue = (ptr(bias_c), ptr(cb_c), mode, ptr(res_c), ptr(y), ptr(ymax), ptr(ystats))
+        if fill:
+            name, fn = "gn_in", "mulan_conv3x3_fwd_f16x3_gn_in"
+            operands = (ptr(x1), ptr(x2), C1, C2, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), groups, act, eps, ptr(bound),
+                        ptr(st1), ptr(st2), 0 if st1 is None else int(st1.shape[1]), ptr(wp), ptr(wmax), *epilogue,
+                        ptr(ys) if want_planes else None, B, H, W, N)
+        else:
+            name, fn = "planes_in", "mulan_conv3x3_fwd_f16x3_planes_in_stats"
+            operands = (ptr(ys), ptr(bound), ptr(wp), ptr(wmax), *epilogue, 1, B, H, W, Ct, N)
+        _timed(f"conv3x3_f16x3_kernel<{name}>", 2.0 * B * HW * 9 * Ct * N, lambda: call(fn, *operands, stream()))
         _leave_maxima(y, ymax)
         if ystats is not None:
             _leave(y, "_gnstats", ystats)
-        ctx.save_for_backward(x1, x2, gamma, beta, mean, rstd, ys, w, bound)
-        ctx.meta = meta
-        ctx.wmax = wmax
-        ctx.has = (bias is not None, None if cbias is None else cbias.dim(), res is not None)
-        ctx.gv_gn = (_gv(gamma), _gv(beta))
-        ctx.gv_conv = (_gv(w), _gv(bias))
-        ctx.bias_sink = _bias_sink_of(x1, C1)
-        if ctx.gv_conv[1] is not None and ctx.needs_input_grad[5]:
-            _leave_bias_sink(y, ctx.gv_conv[1], res)
-        ctx.skip = bool(skip)
-        ctx.has2 = x2 is not None
-        if res is None and mode != 2 and grad_planes_eligible(Ct, N):
+        gn = _GnBwd(saved=(x1, x2, gamma, beta, mean, rstd), gv=(_gv(gamma), _gv(beta)), bias_sink=_bias_sink_of(x1, C1),
+                    meta=(groups, act, 1.0, 0, 0) if fill else (groups, act, keep, seed, offset), keepbits=keepbits)
+        # (planes = False when the kernel needs no gradient -- the ODE evaluator differentiates with respect to the input
+        # only: input gradient without plane output, no weight-gradient launch)
+        conv = _ConvBwd(saved=(ys, w), planes=want_planes, xmax=bound, wmax=wmax, has=_has(bias, cbias, res),
+                        gv=(_gv(w), _gv(bias)), need=(True,) + tuple(need[4:8]))
+        return GnConv3x3Fn._finish_forward(ctx, gn, conv, y, res, skip)
+
+    @staticmethod
+    def _finish_forward(ctx, gn, conv, y, res, skip):
+        """keeps the two records for backward (their tensors through save_for_backward) and tags the output"""
+        ctx.save_for_backward(*gn.saved, *conv.saved, conv.xmax)
+        ctx.gn = gn._replace(saved=())
+        ctx.conv = conv._replace(saved=(), xmax=None)
+        if conv.gv[1] is not None and conv.need[2]:
+            _leave_bias_sink(y, conv.gv[1], res)
+        Ct, N = conv.saved[1].shape[2:]
+        if res is None and conv.has[1] in (None, 2) and grad_planes_eligible(Ct, N):      # (no per-pixel cbias)
             _leave(y, "_accepts_grad_planes")        # this op's backward understands a planes-only output gradient
-        return _skip_outputs(ctx, y, x1, x2) if skip else y
+        return _skip_outputs(y, *gn.saved[:2]) if skip else y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy, ds1=None, ds2=None):
         nones = (None,) * 8
-        box = getattr(ctx, "grad_box", None)
         add1b = None
-        if box is not None:
-            add1b = box.take()
+        if ctx.grad_box is not None:
+            add1b = ctx.grad_box.take()
         if dy is None:     # only the skip path was used downstream
             if add1b is not None:
                 ds1 = add1b if ds1 is None else ds1 + add1b
             return (ds1, ds2) + (None,) * 6 + nones
-        x1, x2, gamma, beta, mean, rstd, ys, w, bound = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        planes_out = ctx.x1_grad_planes and GRAD_PLANES and ds1 is None and add1b is None
-        # (planes = False when the kernel needs no gradient -- the ODE evaluator differentiates with respect to the input
-        # only: input gradient without plane output, no weight-gradient launch)
-        conv = _Ctx(saved_tensors=(ys, w), planes=bool(need[4]), xmax=bound, wmax=ctx.wmax, has=ctx.has, gv=ctx.gv_conv,
-                    needs_input_grad=(True, need[4], need[5], need[6], need[7]), want_dx_max=planes_out)
+        *gn_saved, ys, w, bound = ctx.saved_tensors
+        planes_out = bool(ctx.x1_grad_planes and GRAD_PLANES and ds1 is None and add1b is None)
+        conv = ctx.conv._replace(saved=(ys, w), xmax=bound, want_dx_max=planes_out)
         dh, dw, dbias, dcb, dres = _conv3x3_backward(conv, dy)
-        gn = _Ctx(saved_tensors=(x1, x2, gamma, beta, mean, rstd), meta=ctx.meta, gv=ctx.gv_gn,
-                  bias_sink=ctx.bias_sink, keepbits=ctx.keepbits)
+        gn = ctx.gn._replace(saved=tuple(gn_saved))
         dx1, dx2, dgamma, dbeta = _gn_backward(gn, dh, ds1, ds2, planes_out=planes_out, add1b=add1b)
         return (dx1, dx2, dgamma, dbeta, dw, dbias, dcb, dres) + nones
 

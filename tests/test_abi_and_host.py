@@ -531,6 +531,61 @@ def test_plane_hand_over_gating_and_backward_scope(monkeypatch):
     assert not any(c[0] == "mulan_set_tuning" for c in calls)       # the product path never touches the dev switches
 
 
+def test_gn_reduction_grid_gating_table_and_backward_records(monkeypatch):
+    """host logic, no GPU needed: ops.gn_reduce_grid_ok (the condition gn_conv_ok and both kernel choices of the
+    GroupNorm backward share), ops.gn_conv_ok and ops.grad_planes_eligible over a table of channel counts, output
+    widths, group counts and both arithmetic modes, against the boolean expressions they had as three separate copies
+    (written out below, slot count 16).  An empty channel list (C1 = C2 = 0, never a real layer) divides by zero in the
+    expression as it does in the functions: the table compares that outcome too.  Then the two records the backward
+    functions take: a missing or misspelt field is an error where the record is built, the optional ones default."""
+    import itertools
+    from mulan_amd import ops
+
+    def outcome(f):
+        try:
+            return bool(f())
+        except ZeroDivisionError:
+            return "ZeroDivisionError"
+
+    monkeypatch.setattr(ops, "GN_CONV_PLANES", True)
+    monkeypatch.setattr(ops, "GRAD_PLANES", True)
+    chans = (0, 32, 48, 64, 128, 256, 512)
+    rows = 0
+    for mode in ("f16x3", "f32"):
+        monkeypatch.setattr(ops, "CONV_MODE", mode)
+        f16 = mode == "f16x3"
+        for C1, C2, N, groups in itertools.product(chans, chans, (3, 64, 128, 256, 512), (3, 32)):
+            Ct = C1 + C2
+            cpg = Ct // groups
+            where = (mode, C1, C2, N, groups)
+            assert outcome(lambda: ops.gn_reduce_grid_ok(C1, C2, groups)) == outcome(
+                lambda: C1 % 32 == 0 and C2 % 32 == 0 and Ct // 32 <= 16 and cpg % 4 == 0 and 32 % cpg == 0), where
+            assert outcome(lambda: ops.gn_conv_ok(C1, C2, N, groups)) == outcome(
+                lambda: f16 and Ct % 128 == 0 and N % 128 == 0 and Ct // 32 <= 16 and C1 % 32 == 0 and C2 % 32 == 0 and
+                Ct % groups == 0 and cpg % 4 == 0 and 32 % cpg == 0), where
+            assert ops.grad_planes_eligible(Ct, N) == (f16 and Ct % 128 == 0 and N % 128 == 0 and N % 32 == 0 and
+                                                       Ct % 128 == 0 and N // 32 <= 16), where
+            rows += 1
+    assert rows == 2 * 7 * 7 * 5 * 2
+    monkeypatch.setattr(ops, "CONV_MODE", "f16x3")
+    assert ops.gn_conv_ok(128, 0, 128, 32) and ops.grad_planes_eligible(128, 128)
+    monkeypatch.setattr(ops, "GN_CONV_PLANES", False)
+    monkeypatch.setattr(ops, "GRAD_PLANES", False)
+    assert not ops.gn_conv_ok(128, 0, 128, 32) and not ops.grad_planes_eligible(128, 128)
+
+    conv = dict(saved=(), planes=False, xmax=None, wmax=None, has=(False, None, False), gv=(None, None), need=(True,) * 5)
+    gn = dict(saved=(), meta=(32, 1, 1.0, 0, 0), gv=(None, None), bias_sink=None)
+    assert ops._ConvBwd(**conv).want_dx_max is False and ops._GnBwd(**gn).keepbits is None
+    for record, fields in ((ops._ConvBwd, conv), (ops._GnBwd, gn)):
+        for name in fields:
+            with pytest.raises(TypeError):
+                record(**{k: v for k, v in fields.items() if k != name})
+        with pytest.raises(TypeError):
+            record(**fields, keep_bits=None)
+        with pytest.raises(AttributeError):
+            record(**fields).want_max
+
+
 # ------------------------------------------------------------------------------ round 3: schedule, stream sync, hazards
 def test_lr_schedule_matches_oracle_and_reference_edge_cases():
     """H1: the product's Experiment.get_lr_schedule against the oracle's restatement of ldm/experiment.py:106-129 for

@@ -338,6 +338,40 @@ def test_f16x3_linear_autograd_matches_fp32_gemm(ops, monkeypatch):
         assert float((a - b).abs().max() / a.abs().max()) < 1e-5
 
 
+@pytest.mark.parametrize("x32", [True, False])
+def test_linear2_weight_gradient_takes_its_operand_from_either_hand_over(ops, monkeypatch, x32):
+    """Linear2Fn as the up path's nin_shortcut, its output the residual input of a 3x3 convolution whose backward leaves
+    the planes of the shared dy: the weight gradient reads the fp32 inputs (LINEAR_WGRAD_X32, the default) or the planes
+    its own forward kernel wrote (the switch off: no other test runs that side).  Output and all gradients against
+    float64, at the bar of test_f16x3_linear_autograd_matches_fp32_gemm."""
+    import torch.nn.functional as F
+    torch.manual_seed(2)
+    B, K, N = 2, 128, 128
+    mk = lambda *s, scale=1.0: (torch.randn(*s, device="cuda") * scale).requires_grad_(True)
+    x1, x2, h = mk(B, 1024, K), mk(B, 1024, K), mk(B, 1024, N)
+    w, bias, wc = mk(2 * K, N, scale=0.05), mk(N), mk(3, 3, N, N, scale=0.03)
+    g = torch.randn(B, 1024, N, device="cuda")
+    leaves = (x1, x2, h, w, bias, wc)
+    d = [t.detach().double().cpu().requires_grad_(True) for t in leaves]
+    conv = F.conv2d(d[2].view(B, 32, 32, N).permute(0, 3, 1, 2), d[5].permute(3, 2, 0, 1), padding=1).permute(0, 2, 3, 1)
+    ref_y = conv.reshape(B, 1024, N) + torch.cat((d[0], d[1]), -1) @ d[3] + d[4]
+    ref_y.backward(g.double().cpu())
+    names = []
+    real = ops.call
+    monkeypatch.setattr(ops, "call", lambda n, *a: (names.append(n), real(n, *a))[1])
+    monkeypatch.setattr(ops, "CONV_MODE", "f16x3")
+    monkeypatch.setattr(ops, "LINEAR_WGRAD_X32", x32)
+    y = ops.conv3x3(h, wc, None, None, ops.linear2(x1, x2, w, bias))
+    y.backward(g)
+    kernels = ("mulan_linear_wgrad_f16x3_x32", "mulan_linear_wgrad_f16x3_planes")
+    assert [n for n in names if n in kernels] == [kernels[0 if x32 else 1]]
+    for nm, a, r in zip(("y", "x1", "x2", "h", "w", "bias", "wc"), [y.detach()] + [t.grad for t in leaves],
+                        [ref_y.detach()] + [t.grad for t in d]):
+        err = float((a.double().cpu() - r).abs().max() / r.abs().max())
+        print(f"linear2 x32={x32} {nm}: {err:.3g} (bar 1e-5)")
+        assert err < 1e-5, (nm, err)
+
+
 def test_conv_and_gn_backward_leave_maxima(ops):
     """by-products: the f16x3 convolution leaves the maxima of its output, GroupNorm backward those of its input
     gradients; both equal a pass over the tensor"""

@@ -993,3 +993,31 @@ def test_autograd_wiring_of_group_norm_and_skip(ops):
         check_groups(tag + " dx", torch.cat((x1.grad, x2.grad), -1), c.dx_total(skip, skip), c.G)
         check_each(tag + " dgamma", gamma.grad, c.dgamma)
         check_each(tag + " dbeta", beta.grad, c.dbeta)
+
+
+@pytest.mark.parametrize("sinks", ["fresh", "unaligned"])
+def test_autograd_wiring_off_the_in_kernel_reduction_grid(ops, monkeypatch, sinks):
+    """ops.group_norm_skip over 17 slabs of 32 channels (512 + 32, the narrowest concat the family's shape check takes
+    that has more slabs than the in-kernel reductions have slots): the backward is mulan_groupnorm_bwd_dyn with the sums
+    over the samples in launches of their own -- mulan_colsum_pair into fresh gradients, two mulan_colsum where the
+    registered sinks are not 16-byte aligned.  Output and all four gradients against the float64 reference at the bars of
+    test_autograd_wiring_of_group_norm_and_skip, the skip-path gradients added in the kernel."""
+    c = case(2, 512, 32, 17, 1, 0.9)
+    names = []
+    real = ops.call
+    monkeypatch.setattr(ops, "call", lambda n, *a: (names.append(n), real(n, *a))[1])
+    x1, x2, gamma, beta = (t.clone().requires_grad_() for t in (c.x1, c.x2, c.gamma, c.beta))
+    if sinks == "unaligned":        # views of a gradient buffer one float past a 16-byte boundary, as TrainState registers them
+        gamma._gview, beta._gview = (torch.zeros(c.Ct + 4, device="cuda")[1:1 + c.Ct] for _ in range(2))
+        assert gamma._gview.data_ptr() % 16 == 4
+    out, s1, s2 = ops.group_norm_skip(x1, x2, gamma, beta, groups=c.G, eps=EPS, act=True, keep=0.9, seed=SEED, offset=OFFSET)
+    ((out * c.dy).sum() + (s1 * c.add1).sum() + (s2 * c.add2).sum()).backward()
+    bwd = [n for n in names if n.startswith(("mulan_groupnorm_bwd", "mulan_colsum"))]
+    assert bwd == ["mulan_groupnorm_bwd_dyn"] + (["mulan_colsum_pair"] if sinks == "fresh" else ["mulan_colsum"] * 2), bwd
+    check_groups("off-grid y", out.detach(), c.y, c.G)
+    assert torch.equal(out.detach() != 0, c.mask & (c.y != 0))
+    check_groups("off-grid dx", torch.cat((x1.grad, x2.grad), -1), c.dx_total(True, True), c.G)
+    check_each("off-grid dgamma", gamma.grad, c.dgamma)
+    check_each("off-grid dbeta", beta.grad, c.dbeta)
+    if sinks == "unaligned":        # written where the parameters' gradients live, adopted without a copy
+        assert gamma.grad.data_ptr() == gamma._gview.data_ptr() and beta.grad.data_ptr() == beta._gview.data_ptr()
