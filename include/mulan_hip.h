@@ -666,6 +666,32 @@ size_t mulan_spectrum_workspace(int N, int gray, int blocks);
 int mulan_spectrum(const void* x, int dtype, float scale, float offset, int N, int gray, float* coef, float* radial,
                    double* sum1, double* sum2, int accumulate, int blocks, void* workspace, size_t workspace_bytes,
                    mulan_stream_t stream);
+/* Exact t-SNE into two dimensions (tsne.hip), what sklearn.manifold.TSNE(method='exact') computes, for 4 <= N <= 16384
+ * points; fp32 throughout, the sums over the points in fp64.
+ * mulan_tsne_affinities: x [N][D] -> P [N][N].
+ *   The squared distances sum_d (x_id - x_jd)^2 are taken from the differences.  Per row i, less the row's minimum over
+ *   j != i, beta_i is searched so that the entropy of p_j = exp(-beta_i d_ij) (j != i) is ln(perplexity) nats: beta starts
+ *   at 1 and doubles or halves while a side is open, then 64 midpoint steps, at most 100 steps in all, no tolerance and no
+ *   early exit.  The row becomes P_{j|i} = p_j / sum_j p_j with P_{i|i} = 0; beta [N] (may be NULL) receives beta_i.
+ *   symmetrise    1: P is replaced by (P_{j|i} + P_{i|j}) / (2 N), which sums to 1; 0: the conditional rows stay
+ * mulan_tsne_gradient: one pass over P [N][N] and the map Y [N][2], w_ij = 1 / (1 + |y_i - y_j|^2), w_ii = 0, Z = sum w_ij:
+ *   grad [N][2]   4 (exaggeration sum_j P_ij w_ij (y_i - y_j) - sum_j w_ij^2 (y_i - y_j) / Z)
+ *   kl            may be NULL; one fp64: sum_{P_ij > 0} P_ij ln(P_ij / (w_ij / Z)), of P as it is passed (no exaggeration)
+ *   workspace     mulan_tsne_workspace(N) bytes (0 for an N that is refused), 16-byte aligned
+ * mulan_tsne_update: sklearn's _gradient_descent body on every element of Y, U (the update), G (the gains), all [N][2]:
+ *   G += 0.2 where U grad < 0, else G *= 0.8; G = max(G, 0.01); U = momentum U - lr G grad; Y += U.  No recentring.
+ * Every sum is taken in one fixed order and there are no atomics: the same arguments give the same bits.  P, Y and the
+ * workspace must be 16-byte aligned, kl 8-byte, the other arrays 4-byte.
+ * hipErrorInvalidValue, before anything is launched, for N outside 4..16384, D < 1, perplexity outside [1, N - 1) (or
+ * NaN), symmetrise outside 0..1, a NULL x / P / Y / grad / U / G / workspace, workspace_bytes below
+ * mulan_tsne_workspace(N), exaggeration or lr not positive and finite, momentum outside [0, 1), a misaligned pointer. */
+size_t mulan_tsne_workspace(int N);
+int mulan_tsne_affinities(const float* x, int N, int D, float perplexity, int symmetrise, float* P, float* beta,
+                          mulan_stream_t stream);
+int mulan_tsne_gradient(const float* P, const float* Y, int N, float exaggeration, float* grad, double* kl,
+                        void* workspace, size_t workspace_bytes, mulan_stream_t stream);
+int mulan_tsne_update(const float* grad, float* Y, float* U, float* G, int N, float momentum, float lr,
+                      mulan_stream_t stream);
 /* _topk_embedding_and_loss + _gamma_noise + _gumbel_kl_loss (model_mulan_velocity.py:78-120).
  * gnoise: [10,B,L] raw Gamma(1/k,1) draws; tau < 0: gnoise is [B,L] additive noise (topk_noise_type 'gumbel',
  * model_mulan_epsilon.py:236-239); gnoise = NULL: hard k-hot of the plain logits (soft / nrm may be NULL). */

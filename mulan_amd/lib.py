@@ -100,6 +100,10 @@ SIGNATURES = {
     "mulan_knn_u8": [P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P],
     "mulan_spectrum_workspace": [I, I, I],
     "mulan_spectrum": [P, I, F, F, I, I, P, P, P, P, I, I, P, Z, P],
+    "mulan_tsne_workspace": [I],
+    "mulan_tsne_affinities": [P, I, I, F, I, P, P, P],
+    "mulan_tsne_gradient": [P, P, I, F, P, P, P, Z, P],
+    "mulan_tsne_update": [P, P, P, P, I, F, F, P],
     "mulan_topk_fwd": [P, P, P, P, P, P, I, I, I, F, P],
     "mulan_topk_bwd": [P, P, P, P, P, P, I, I, P],
     "mulan_gumbel_latent_fwd": [P, P, P, P, P, P, I, I, P],
@@ -145,7 +149,7 @@ SIGNATURES = {
     "mulan_stream_wait_signal": [P, P, ctypes.c_uint],
     "mulan_signal_read": [P, P],
 }
-_RESTYPES = {"mulan_rk_workspace_bytes": c_size_t, "mulan_bound_profile_workspace": c_size_t, "mulan_knn_u8_workspace": c_size_t, "mulan_spectrum_workspace": c_size_t, "mulan_global_norm_clip_workspace": c_size_t, "mulan_conv3x3_wgrad_workspace": c_size_t, "mulan_conv3x3_pack_f16x3_bytes": c_size_t, "mulan_conv3x3_planes_bytes": c_size_t, "mulan_linear_pack_f16x3_bytes": c_size_t,
+_RESTYPES = {"mulan_rk_workspace_bytes": c_size_t, "mulan_bound_profile_workspace": c_size_t, "mulan_knn_u8_workspace": c_size_t, "mulan_spectrum_workspace": c_size_t, "mulan_tsne_workspace": c_size_t,"mulan_global_norm_clip_workspace": c_size_t, "mulan_conv3x3_wgrad_workspace": c_size_t, "mulan_conv3x3_pack_f16x3_bytes": c_size_t, "mulan_conv3x3_planes_bytes": c_size_t, "mulan_linear_pack_f16x3_bytes": c_size_t,
              "mulan_linear_wgrad_f16x3_planes_workspace": c_size_t, "mulan_linear_wgrad_f16x3_x32_workspace": c_size_t,
              "mulan_conv3x3_wgrad_f16x3_planes_workspace": c_size_t, "mulan_conv3x3_wgrad_f16x3_workspace": c_size_t, "mulan_gemm_workspace": c_size_t, "mulan_version": c_char_p}
 

@@ -2502,6 +2502,108 @@ def spectrum(x, *, scale=1.0, offset=0.0, gray=False, coef=False, radial=False, 
     return coef_out, radial_out, (sum1, sum2) if sum1 is not None else None
 
 
+TSNE_MIN_N, TSNE_MAX_N = 4, 16384      # the range of mulan_tsne_*: P is dense, 1 GiB at the cap
+
+
+def _tsne_number(name, v, lo=None, lo_open=False, hi=None):
+    """a finite real (not a bool) with lo <= v (lo < v with lo_open) and v < hi -> float"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+        raise ValueError(f"tsne: {name} is a finite number, got {v!r}")
+    if (lo is not None and (v <= lo if lo_open else v < lo)) or (hi is not None and v >= hi):
+        raise ValueError(f"tsne: {name} lies in {'(' if lo_open else '['}{lo}, {hi if hi is not None else 'inf'}), got {v!r}")
+    return float(v)
+
+
+def _tsne_array(name, v, shape, dtype="float32"):
+    if not hasattr(v, "dtype") or str(v.dtype).replace("torch.", "") != dtype or tuple(v.shape) != tuple(shape):
+        raise ValueError(f"tsne: {name} is {dtype} {list(shape)}; got "
+                         f"{(v.dtype, tuple(v.shape)) if hasattr(v, 'dtype') else type(v).__name__}")
+    if torch.is_tensor(v) and not v.is_contiguous():
+        raise ValueError(f"tsne: {name} is contiguous")
+
+
+def tsne_affinities_check(x, perplexity, symmetrise=True, return_beta=False):
+    """every check of tsne_affinities that needs no library call; x: anything with dtype and shape -> (N, D)"""
+    if not hasattr(x, "dtype") or str(x.dtype) not in ("torch.float32", "float32") or len(x.shape) != 2 \
+            or not TSNE_MIN_N <= x.shape[0] <= TSNE_MAX_N or x.shape[1] < 1:
+        raise ValueError(f"tsne: x is fp32 [N, D] with {TSNE_MIN_N} <= N <= {TSNE_MAX_N} and D >= 1; got "
+                         f"{(x.dtype, tuple(x.shape)) if hasattr(x, 'dtype') else type(x).__name__}")
+    N, D = x.shape
+    _tsne_number("perplexity", perplexity, lo=1, hi=N - 1)
+    for name, v in (("symmetrise", symmetrise), ("return_beta", return_beta)):
+        if not isinstance(v, bool):
+            raise ValueError(f"tsne: {name} is a bool, got {v!r}")
+    return N, D
+
+
+def tsne_affinities(x, perplexity, symmetrise=True, return_beta=False):
+    """P, fp32 [N, N], of the rows of x (fp32 [N, D] on the device): the affinities of exact t-SNE (mulan_tsne_affinities).
+    Row i holds P_{j|i}, the Gaussian around x_i whose perplexity is `perplexity` (1 <= perplexity < N - 1), from squared
+    distances taken from the differences; with symmetrise (P_{j|i} + P_{i|j}) / (2 N), which sums to 1.  return_beta:
+    (P, beta) with beta fp32 [N], the precisions 1 / (2 sigma_i^2) the search ended at.  The same call gives the same
+    bits."""
+    N, D = tsne_affinities_check(x, perplexity, symmetrise, return_beta)
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ValueError("tsne: x is a tensor on the device")
+    x = _c(x)
+    P = torch.empty((N, N), device=x.device, dtype=torch.float32)
+    beta = torch.empty(N, device=x.device, dtype=torch.float32) if return_beta else None
+    call("mulan_tsne_affinities", ptr(x), N, D, float(perplexity), int(symmetrise), ptr(P), ptr(beta), stream())
+    return (P, beta) if return_beta else P
+
+
+def tsne_step_check(P, Y, U, G, exaggeration, momentum, lr, kl=False):
+    """every check of tsne_step that needs no library call -> N"""
+    if not hasattr(P, "shape") or len(P.shape) != 2 or P.shape[0] != P.shape[1] or not TSNE_MIN_N <= P.shape[0] <= TSNE_MAX_N:
+        raise ValueError(f"tsne: P is fp32 [N, N] with {TSNE_MIN_N} <= N <= {TSNE_MAX_N}; got "
+                         f"{tuple(P.shape) if hasattr(P, 'shape') else type(P).__name__}")
+    N = P.shape[0]
+    _tsne_array("P", P, (N, N))
+    for name, v in (("Y", Y), ("U", U), ("G", G)):
+        _tsne_array(name, v, (N, 2))
+    _tsne_number("exaggeration", exaggeration, lo=0, lo_open=True)
+    _tsne_number("momentum", momentum, lo=0, hi=1)
+    _tsne_number("lr", lr, lo=0, lo_open=True)
+    if not isinstance(kl, bool):
+        _tsne_array("kl", kl, (), "float64")
+    return N
+
+
+def tsne_step(P, Y, U, G, exaggeration, momentum, lr, kl=False):
+    """One iteration of exact t-SNE, in place on the map Y, its update U and the gains G (fp32 [N, 2] each) under the
+    affinities P (fp32 [N, N]): mulan_tsne_gradient (one pass over P, then the fold) and mulan_tsne_update (sklearn's
+    delta-bar-delta body; no recentring).  kl: True returns the Kullback-Leibler divergence of the map BEFORE the update,
+    of P as passed, as a 0-d fp64 tensor on the device (no host read); a 0-d fp64 device tensor is written instead of a
+    fresh one; False returns None and the launch holds no logarithm."""
+    N = tsne_step_check(P, Y, U, G, exaggeration, momentum, lr, kl)
+    for name, v in (("P", P), ("U", U), ("G", G)):
+        if not torch.is_tensor(v) or not v.is_cuda or v.device != P.device:
+            raise ValueError(f"tsne: {name} is a tensor on the device of P")
+    grad, out = tsne_gradient(P, Y, exaggeration, kl)
+    call("mulan_tsne_update", ptr(grad), ptr(Y), ptr(U), ptr(G), N, float(momentum), float(lr), stream())
+    return out
+
+
+def tsne_gradient(P, Y, exaggeration=1.0, kl=False):
+    """(grad fp32 [N, 2], kl): the gradient pass of tsne_step alone, nothing updated; kl as in tsne_step"""
+    N = tsne_step_check(P, Y, Y, Y, exaggeration, 0.5, 1.0, kl)
+    for name, v in dict(P=P, Y=Y, **({} if isinstance(kl, bool) else dict(kl=kl))).items():
+        if not torch.is_tensor(v) or not v.is_cuda or v.device != P.device:
+            raise ValueError(f"tsne: {name} is a tensor on the device of P")
+    dev = P.device
+    out = torch.empty((), device=dev, dtype=torch.float64) if kl is True else (None if kl is False else kl)
+    nbytes = lib.load().mulan_tsne_workspace(N)
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    grad = torch.empty((N, 2), device=dev, dtype=torch.float32)
+    call("mulan_tsne_gradient", ptr(P), ptr(Y), N, float(exaggeration), ptr(grad), ptr(out), ptr(ws), nbytes, stream())
+    return grad, out
+
+
+def tsne_kl(P, Y, out=None):
+    """the Kullback-Leibler divergence of the map Y under P: a 0-d fp64 device tensor (`out`, if given, is written)"""
+    return tsne_gradient(P, Y, 1.0, kl=True if out is None else out)[1]
+
+
 # ----------------------------------------------------------------------------- exact-likelihood ODE (eval only)
 def topk_hard(logits, k):
     """(k-hot embedding of the plain logits, KL(softmax(logits) || uniform)): notebook_utils.logits_to_embeddings and
