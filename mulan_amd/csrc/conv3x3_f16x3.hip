@@ -52,6 +52,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16x3_v2_kernel(ConvArgsH p) {
   float sx, inv_x, sw, inv_w;
   scale_of(row_max16(p.xmax, b), sx, inv_x);
   scale_of(row_max16(p.wmax, 0), sw, inv_w);
+  balance_pow2(inv_x, inv_w);
 
   f32x16 acc[MT][NT];
 #pragma unroll
@@ -84,9 +85,11 @@ __global__ __launch_bounds__(256) void conv3x3_f16x3_v2_kernel(ConvArgsH p) {
     const bool interior = inb && prow >= 1 && prow <= TR2 && ww >= 0 && ww < kW;
     pemit[s] = interior ? (unsigned)(((hh * kW + ww) * 2) * 32 + q * 8) : 0xffffffffu;
   }
-  // plane output window of this block: image b (nothing for the other cout blocks, or when not requested)
+  // plane output window of this block: image b (nothing for the other cout blocks, or when not requested);
+  // chunk_b: bytes of one 16-channel chunk of one image, [H * W][plane][16] fp16
+  const unsigned chunk_b = (unsigned)(p.H * kW * 64);
   const __amdgpu_buffer_rsrc_t xs_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.xs + (size_t)b * nchunks * 65536, 0, (p.xs && blockIdx.y == 0) ? nchunks * 65536 : 0, kBufWord3);
+      p.xs + (size_t)b * nchunks * chunk_b, 0, (p.xs && blockIdx.y == 0) ? (int)(nchunks * chunk_b) : 0, kBufWord3);
   i32x4 preg[PV];
   auto gload_patch = [&](int cc) {
 #pragma unroll
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(256) void conv3x3_f16x3_v2_kernel(ConvArgsH p) {
     *reinterpret_cast<f16x4*>(d) = hi;
     *reinterpret_cast<f16x4*>(d + 32) = lo;
     // the same two quads go to the plane tensor (consumed by the weight-gradient kernel)
-    const unsigned eo = pemit[s] != 0xffffffffu ? pemit[s] + (unsigned)cc * 65536u : 0xffffffffu;
+    const unsigned eo = pemit[s] != 0xffffffffu ? pemit[s] + (unsigned)cc * chunk_b : 0xffffffffu;
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, hi), xs_rsrc, eo, 0, 0);
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, lo), xs_rsrc, eo == 0xffffffffu ? eo : eo + 32, 0, 0);
   };

@@ -154,8 +154,9 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3x3_f16x3_v3_ke
       const_cast<float*>(p.x), 0, (int)((size_t)p.B * p.H * kW * ldx * 4), kBufWord3);
   const __amdgpu_buffer_rsrc_t wp_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<unsigned char*>(p.wp), 0, 9 * C * N * 4, kBufWord3);
+  const unsigned chunk_b = (unsigned)(p.H * kW * 64);   // bytes of one 16-channel chunk of one image's planes: [H * W][plane][16]
   const __amdgpu_buffer_rsrc_t xs_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.xs + (size_t)b * nchunks * 65536, 0, (p.xs && by == 0) ? nchunks * 65536 : 0, kBufWord3);
+      p.xs + (size_t)b * nchunks * chunk_b, 0, (p.xs && by == 0) ? (int)(nchunks * chunk_b) : 0, kBufWord3);
 
   // ---- patch slots of the fp32-input fills (PIN fills by DMA, further down): slot = tid + 256 s -> (pixel of the
   // 10 x 34 halo patch, channel quad q = tid & 3).  The slot geometry is recomputed where it is used (from a laundered
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3x3_f16x3_v3_ke
     *reinterpret_cast<f16x4*>(d) = hi;
     *reinterpret_cast<f16x4*>(d + (sl.ldst >= P3_DUMMY ? 0 : P3_PLANE)) = lo;
     if (GNF == 1) return;
-    const unsigned eo = sl.emit != 0xffffffffu ? sl.emit + (unsigned)cc * 65536u : 0xffffffffu;
+    const unsigned eo = sl.emit != 0xffffffffu ? sl.emit + (unsigned)cc * chunk_b : 0xffffffffu;
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, hi), xs_rsrc, eo, 0, 0);
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, lo), xs_rsrc, eo == 0xffffffffu ? eo : eo + 32, 0, 0);
   };
@@ -532,6 +533,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3x3_f16x3_v3_ke
   if (GNF != 0 && p.xstats) scale_of(__float_as_uint(*reinterpret_cast<const float*>(smem + GN_SLOT)), sx, inv_x);
   else scale_of(row_max16(p.xmax, b), sx, inv_x);    // (re-derived here: nothing of it lives across the main loop)
   scale_of(row_max16(p.wmax, 0), sw, inv_w);
+  balance_pow2(inv_x, inv_w);
   constexpr int HPT = NPT / 2;
   if constexpr (KS == 2) {
     // the groups swap halves: group 0 keeps pixel tiles [0, HPT) and receives group 1's sums for them, group 1 the rest.

@@ -21,6 +21,17 @@ __device__ __forceinline__ void scale_of(unsigned maxbits, float& s, float& inv)
   inv = __uint_as_float((unsigned)(e - 13) << 23);
 }
 
+// The two factors that take an accumulator (in units of s_a s_b) back to the operands' units, rebalanced: inv_a inv_b = 2^E
+// as two powers of two of (nearly) equal exponent.  (acc * a) * b then leaves the fp32 range only where the result itself
+// does -- unbalanced, acc * inv_a alone overflows for an image of magnitude 2^110 and more (inv_a >= 2^97, acc up to
+// 2^38) whatever the weights are.  Both factors are exact, so every result that was in range keeps its bits.
+__device__ __forceinline__ void balance_pow2(float& a, float& b) {
+  const int E = (int)(__float_as_uint(a) >> 23) + (int)(__float_as_uint(b) >> 23) - 254;   // a, b: positive, normal
+  const int E1 = E >> 1;
+  a = __uint_as_float((unsigned)(E1 + 127) << 23);
+  b = __uint_as_float((unsigned)(E - E1 + 127) << 23);
+}
+
 // Maxima arrays hold kMaxParts partial maxima per row (fp32 bit patterns; producers write their partials without
 // atomics or a zero-fill pass, unused entries are 0); consumers take the maximum of the 16 entries of a row.
 constexpr int kMaxParts = 16;

@@ -73,6 +73,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_kernel(WgradArgsH p) 
     __syncthreads();
     scale_of(mx, sx, inv_x);
     scale_of(mg, sg, inv_g);
+    balance_pow2(inv_x, inv_g);
   }
 
   f32x16 acc[9];
@@ -285,10 +286,11 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
   constexpr int XV = (X3PIX * 32 + 255) / 256;  // 9 (2176 units)
   constexpr int DV = (DPIX * 32) / 256;         // 8 (2048 units)
   i32x4 xreg[XV], dreg[DV];
+  const int hw = p.H * kW;                       // pixels per image: a chunk of the planes is [hw][plane][16]
   const __amdgpu_buffer_rsrc_t xs_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.xs), 0, p.B * nchc * 65536, kBufWord3);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.xs), 0, p.B * nchc * hw * 64, kBufWord3);
   const __amdgpu_buffer_rsrc_t ds_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.dys), 0, p.B * nchn * 65536, kBufWord3);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.dys), 0, p.B * nchn * hw * 64, kBufWord3);
   const int u = tid & 3, upl = u >> 1, uh = u & 1;
   // fp32 x: float4 unit t = tid + 256 i (i < 8): pixel t >> 5 of the pair's 64, channel quad t & 31 of the 128-ci tile
   const bool x_first = c0 < p.C1;
@@ -313,14 +315,14 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16x3_planes_kernel(WgradAr
     const int prow = pix / kPW, pcol = pix - prow * kPW;
     const int hh = h0 + prow;
     const bool ok = t < 8 * X3PIX && pcol >= 1 && pcol <= kW && hh >= 0 && hh < p.H;
-    const unsigned off = (unsigned)((((b * nchc + (c0 >> 4) + cc) * 1024 + hh * kW + pcol - 1) * 2 + upl) * 32 + uh * 16);
+    const unsigned off = (unsigned)((((b * nchc + (c0 >> 4) + cc) * hw + hh * kW + pcol - 1) * 2 + upl) * 32 + uh * 16);
     xreg[i] = __builtin_amdgcn_raw_buffer_load_b128(xs_rsrc, ok ? off : 0xffffffffu, 0, 0);
   };
   auto gload_d1 = [&](int pr, int i) {
     const int b = pr / pairs_per_img, h0 = (pr - b * pairs_per_img) * WG_ROWS;
     const int t = (tid >> 2) + 64 * i;
     const int cc = t >> 6, pix = t & 63;
-    const unsigned off = (unsigned)((((b * nchn + (n0 >> 4) + cc) * 1024 + h0 * kW + pix) * 2 + upl) * 32 + uh * 16);
+    const unsigned off = (unsigned)((((b * nchn + (n0 >> 4) + cc) * hw + h0 * kW + pix) * 2 + upl) * 32 + uh * 16);
     dreg[i] = __builtin_amdgcn_raw_buffer_load_b128(ds_rsrc, off, 0, 0);
   };
   // branch free (the loop body must stay one basic block): the 128 units past the x tile land in a dummy area
@@ -601,25 +603,26 @@ __global__ __launch_bounds__(W8_THREADS) void conv3x3_wgrad_f16x3_w16_kernel(Wgr
   const int u = tid & 3, upl = u >> 1, uh = u & 1;
   const int spix = (tid >> 2) & 63, scol = spix & 31, scc = (tid >> 8) & 1;
   const int wrow = (wave & 3) >> 1;
-  const unsigned vlane = (unsigned)(((scc * 1024 + scol) * 2 + upl) * 32 + uh * 16);
+  const unsigned chunk_b = (unsigned)(p.H * kW * 64);   // bytes of one 16-channel chunk of one image: [H * W][plane][16]
+  const unsigned vlane = (unsigned)scc * chunk_b + (unsigned)((scol * 2 + upl) * 32 + uh * 16);
   const int xdst0 = upl * X3_PLANE + (wrow * kPW + scol + 1) * 64 + (scc ^ (((scol + 1) >> 3) & 1)) * 32 + uh * 16;
   const int ddst0 = 2 * X3_PLANE + upl * D3_PLANE + spix * 64 + (scc ^ ((scol >> 3) & 1)) * 32 + uh * 16;
-  const unsigned xtile = (unsigned)((c0 >> 4) * 65536), dtile = (unsigned)((n0 >> 4) * 65536);
+  const unsigned xtile = (unsigned)(c0 >> 4) * chunk_b, dtile = (unsigned)(n0 >> 4) * chunk_b;
   // fetch pointer (the pair whose loads are being issued): image fb, pair fr inside it; scalar offsets and lane word
   int fb = 0, fr = 0;
   unsigned sx = 0, sd = 0, vx = vlane;
   auto set_fetch = [&](int b, int r) {
     fb = b; fr = r;
     const int hx = r * WG_ROWS + kh - 1 + wrow;                        // image row of this wave's x units
-    sx = (unsigned)(b * nchc) * 65536u + xtile + (unsigned)(hx * (kW * 64));
-    sd = (unsigned)(b * nchn) * 65536u + dtile + (unsigned)((r * WG_ROWS + wrow) * (kW * 64));
+    sx = (unsigned)(b * nchc) * chunk_b + xtile + (unsigned)(hx * (kW * 64));
+    sd = (unsigned)(b * nchn) * chunk_b + dtile + (unsigned)((r * WG_ROWS + wrow) * (kW * 64));
     vx = vlane | ((unsigned)hx >= (unsigned)p.H ? 0x80000000u : 0u);
   };
   auto gload_x1 = [&](int i) {
-    xreg[i] = __builtin_amdgcn_raw_buffer_load_b128(xs_rsrc, vx, sx + (unsigned)i * 131072u, 0);
+    xreg[i] = __builtin_amdgcn_raw_buffer_load_b128(xs_rsrc, vx, sx + (unsigned)i * 2u * chunk_b, 0);
   };
   auto gload_d1 = [&](int i) {
-    dreg[i] = __builtin_amdgcn_raw_buffer_load_b128(ds_rsrc, vlane, sd + (unsigned)i * 131072u, 0);
+    dreg[i] = __builtin_amdgcn_raw_buffer_load_b128(ds_rsrc, vlane, sd + (unsigned)i * 2u * chunk_b, 0);
   };
   auto store_x = [&](unsigned char* buf, int i) { *reinterpret_cast<i32x4*>(buf + xdst0 + i * X3_HALF) = xreg[i]; };
   auto store_d = [&](unsigned char* buf, int i) { *reinterpret_cast<i32x4*>(buf + ddst0 + i * D3_HALF) = dreg[i]; };
@@ -762,6 +765,7 @@ __global__ __launch_bounds__(W8_THREADS) void conv3x3_wgrad_f16x3_w16_kernel(Wgr
   float sdummy, inv_x, inv_g;
   scale_of(row_max16(p.xmax, b_acc), sdummy, inv_x);
   scale_of(row_max16(p.dymax, b_acc), sdummy, inv_g);
+  balance_pow2(inv_x, inv_g);
   float* slab = p.slab + (size_t)bs * 9 * C * N;
 #pragma unroll
   for (int kw = 0; kw < 3; ++kw)

@@ -26,6 +26,8 @@ def dev(a):
     return torch.as_tensor(np.ascontiguousarray(a)).float().cuda()
 
 
+# (heights other than 32, the packs and planes as bits, the scale clamps and the weight gradients' slabs of this kernel
+# family: tests/test_gpu_conv_f16x3.py)
 @pytest.mark.parametrize("B,C,N", [(2, 128, 128), (1, 256, 128), (1, 128, 256), (1, 16, 128), (3, 48, 128)])
 def test_f16x3_conv_exact_on_integers(ops, B, C, N):
     rng = np.random.default_rng(B + C + N)

@@ -7,8 +7,9 @@ hipErrorInvalidValue and every output buffer still holds its sentinel bytes; A =
 exact on integer data (the bar of tests/test_gpu_f16x3.py and tests/test_gpu_linear_f16x3.py for integers); - = the entry
 point has no such argument, or does not look at it.  Accepted rows run at the smallest shapes the kernels take.
 
-Plane tensors that a weight-gradient kernel reads are laid out with 1024 pixels per image whatever H is; the rows of an
-image past H * 32 hold other integers that a kernel reading past the image's end would sum.
+Plane tensors that a weight-gradient kernel reads have the layout the header documents and the forward kernels write,
+[B][C/16][H * W][plane][16]: H * 32 pixels per image (tests/test_gpu_conv_f16x3.py holds writers and readers to it at
+other heights); the images differ by powers of two, so a kernel that read past an image's end would sum the next one.
 
 The 2 GiB limit is held without a device (test_two_gib_tensors_are_refused_without_a_device): a wrongly accepted call
 would launch over buffers far smaller than its shape claims."""
@@ -220,7 +221,7 @@ def run_wg(ops, entry, B=None, H=None, W=32, C=128, N=128, C2=0, nulls=()):
     H = WG_VALID[entry][1] if H is None else H
     rng = np.random.default_rng(H + C + N + C2)
     Bm, Ct, px = max(B, 1), C + C2, H * 32
-    # [Bm, 1024, channels] with image b at the power of two 2^b; only the first H * 32 pixels of an image belong to it
+    # [Bm, 1024, channels] with image b at the power of two 2^b; the first H * 32 pixels of an image are the call's operand
     x = rng.integers(-3, 4, (Bm, 1024, Ct)) * 2.0 ** np.arange(Bm)[:, None, None]
     dy = rng.integers(-2, 3, (Bm, 1024, N)) * 2.0 ** (3 * np.arange(Bm))[:, None, None]
     xin, dyin = x[:, :px], dy[:, :px]
@@ -244,7 +245,7 @@ def run_wg(ops, entry, B=None, H=None, W=32, C=128, N=128, C2=0, nulls=()):
         rc = L.mulan_conv3x3_wgrad_f16x3(xd.data_ptr(), null(xmax, "xmax", nulls), dyd.data_ptr(), null(dymax, "dymax", nulls),
                                          dw, out["ws"].ptr, B, H, W, C, N, 0, s)
     else:
-        dys, dymax = planes_dev(dy, 1024)
+        dys, dymax = planes_dev(dyin, px)
         dysp, dymaxp = null(dys, "dys", nulls), null(dymax, "dymax", nulls)
         if entry == "linear_x32":
             x1, x2 = dev(xin[..., :C]), (dev(xin[..., C:]) if C2 else None)
@@ -253,7 +254,7 @@ def run_wg(ops, entry, B=None, H=None, W=32, C=128, N=128, C2=0, nulls=()):
                 null(x1, "x", nulls), None if x2 is None or "x2" in nulls else x2.data_ptr(), C, C2, null(m1, "xmax", nulls),
                 None if m2 is None or "xmax2" in nulls else m2.data_ptr(), dysp, dymaxp, dw, out["ws"].ptr, B, H, W, N, 0, 0, s)
         else:
-            xs, xmax = planes_dev(x, 1024)
+            xs, xmax = planes_dev(xin, px)
             a = (null(xs, "x", nulls), null(xmax, "xmax", nulls), dysp, dymaxp, dw)
             if entry == "bmm_tn":
                 rc = L.mulan_bmm_tn_f16x3_planes(*a, B, H, W, C, N, s)
