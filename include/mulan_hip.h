@@ -666,6 +666,31 @@ size_t mulan_spectrum_workspace(int N, int gray, int blocks);
 int mulan_spectrum(const void* x, int dtype, float scale, float offset, int N, int gray, float* coef, float* radial,
                    double* sum1, double* sum2, int accumulate, int blocks, void* workspace, size_t workspace_bytes,
                    mulan_stream_t stream);
+/* Image fidelity of M pairs of 32 x 32 x 3 uint8 images, channels innermost (fidelity.hip): a [Na][32][32][3] against
+ * b [Nb][32][32][3], pair m being (a[ia ? ia[m] : m], b[ib ? ib[m] : m]); ia and ib [M] may be NULL.
+ * Each output may be NULL, not all:
+ *   sse [M][3]          the sum over the 1024 pixels of the squared difference per channel, in integers: exact
+ *   sse_masked [M][3]   the same sum over the pixels whose mask byte is not 0; mask is [M][32][32] with mask_per_pair = 1,
+ *                       one [32][32] for all pairs with 0.  sse_masked and mask come together: both or neither.
+ *   ssim [M][P]         the mean SSIM of Wang et al. (2004): the normalised 11 x 11 Gaussian window of sigma 1.5,
+ *                       w_k ~ exp(-k^2 / 4.5), k = -5..5, applied separably; the biased (population) moments;
+ *                       C1 = (0.01 255)^2, C2 = (0.03 255)^2; over the 22 x 22 windows that lie wholly inside the image --
+ *                       skimage.metrics.structural_similarity(gaussian_weights=True, use_sample_covariance=False,
+ *                       data_range=255), cropped by 5, so no boundary rule enters.  fp32; the moments are taken of the
+ *                       values less 128 and the means shifted back, which keeps E[x^2] - mu^2 from cancelling.
+ *   ssim_map [M][22][22][P]   the per-window values whose mean is ssim
+ *   gray                1: P = 1 and the planes compared are the luma 0.2125 R + 0.7154 G + 0.0721 B, in fp32 and not
+ *                       rounded; 0: P = 3, plane p is channel p.  sse and sse_masked are per channel either way.
+ * Every sum is taken in one fixed order and there are no atomics: the same arguments give the same bits, and an output
+ * does not depend on which others are asked for.  An index outside [0, Na) or [0, Nb) cannot be checked without a read
+ * and is not dereferenced: that pair's sse and sse_masked are -1 and its ssim and ssim_map NaN; other pairs are
+ * unaffected.  a, b and ssim_map must be 16-byte aligned, the int and float arrays 4-byte.
+ * hipErrorInvalidValue, before anything is launched, for M, Na or Nb < 1, M > Na with a NULL ia, M > Nb with a NULL ib,
+ * a NULL a or b, all four outputs NULL, sse_masked without mask or mask without sse_masked, gray or mask_per_pair
+ * outside 0..1, a misaligned pointer. */
+int mulan_image_fidelity(const unsigned char* a, int Na, const unsigned char* b, int Nb, const int* ia, const int* ib,
+                         int M, int gray, const unsigned char* mask, int mask_per_pair, int* sse, int* sse_masked,
+                         float* ssim, float* ssim_map, mulan_stream_t stream);
 /* Exact t-SNE into two dimensions (tsne.hip), what sklearn.manifold.TSNE(method='exact') computes, for 4 <= N <= 16384
  * points; fp32 throughout, the sums over the points in fp64.
  * mulan_tsne_affinities: x [N][D] -> P [N][N].

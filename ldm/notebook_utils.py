@@ -3,8 +3,9 @@ the variational-bound BPD evaluators (:157-191), the exact-likelihood ODE evalua
 the learned noise schedule (:554-711); bound_profile / plot_bound_profile (not in the reference) take the bound apart;
 nearest_neighbours / sample_novelty / precision_recall / plot_neighbours (not in the reference) ask whether samples are new;
 dct2 (:730-733, there on skimage and scipy) and image_spectrum / compare_spectra / schedule_spectrum / plot_spectra (not
-in the reference) look at spatial frequency; pca_transformation, plot_tsne_transformation and animate_scatter (:713-753,
-there on sklearn; here exact t-SNE on the device) and tsne / latent_map (not in the reference) look at the latent space."""
+in the reference) look at spatial frequency; image_fidelity / restoration_quality / diversity / plot_fidelity (not in the
+reference) give the PSNR and SSIM of restorations against their originals; pca_transformation,
+plot_tsne_transformation and animate_scatter (:713-753, there on sklearn; here exact t-SNE on the device) and tsne / latent_map (not in the reference) look at the latent space."""
 from mulan_amd.evaluators import (Experiment_Colab, Hutchinson, eval_bpd_dense_sampling,  # noqa: F401
                                   eval_bpd_ode, eval_bpd_sparse_sampling, get_ode_likelihood_fn, get_logits, get_sample_fn,
                                   logits_to_embeddings, _get_bpd_offset)
@@ -15,5 +16,7 @@ from mulan_amd.neighbours import nearest as nearest_neighbours, novelty as sampl
 from mulan_amd.neighbours import precision_recall, plot_neighbours  # noqa: F401
 from mulan_amd.spectrum import (compare_spectra, dct2, image_spectrum, plot_spectra,  # noqa: F401
                                 schedule_spectrum)
+from mulan_amd.fidelity import (diversity, image_fidelity, plot_fidelity, psnr_from_sse,  # noqa: F401
+                                restoration_quality)
 from mulan_amd.latent_maps import (animate_scatter, latent_map, pca_transformation,  # noqa: F401
                                    plot_tsne_transformation, tsne)

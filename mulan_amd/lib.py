@@ -100,6 +100,7 @@ SIGNATURES = {
     "mulan_knn_u8": [P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P],
     "mulan_spectrum_workspace": [I, I, I],
     "mulan_spectrum": [P, I, F, F, I, I, P, P, P, P, I, I, P, Z, P],
+    "mulan_image_fidelity": [P, I, P, I, P, P, I, I, P, I, P, P, P, P, P],
     "mulan_tsne_workspace": [I],
     "mulan_tsne_affinities": [P, I, I, F, I, P, P, P],
     "mulan_tsne_gradient": [P, P, I, F, P, P, P, Z, P],

@@ -2502,7 +2502,79 @@ def spectrum(x, *, scale=1.0, offset=0.0, gray=False, coef=False, radial=False, 
     return coef_out, radial_out, (sum1, sum2) if sum1 is not None else None
 
 
-TSNE_MIN_N, TSNE_MAX_N = 4, 16384      # the range of mulan_tsne_*: P is dense, 1 GiB at the cap
+FIDELITY_WINDOWS = 22              # SSIM windows per side: the 11 x 11 Gaussian inside a 32 x 32 image
+
+
+def _fidelity_kind(v):
+    return (str(v.dtype).replace("torch.", ""), tuple(v.shape)) if hasattr(v, "dtype") else type(v).__name__
+
+
+def image_fidelity_check(a, b, ia=None, ib=None, gray=False, mask=None, sse=True, ssim=True, ssim_map=False):
+    """every check of image_fidelity that needs no library call; a, b, ia, ib, mask: anything with dtype and shape
+    -> (M, P, mask_per_pair)"""
+    for name, v in (("a", a), ("b", b)):
+        if not hasattr(v, "dtype") or str(v.dtype) not in ("torch.uint8", "uint8") or len(v.shape) != 4 \
+                or tuple(v.shape[1:]) != (32, 32, 3) or v.shape[0] < 1:
+            raise ValueError(f"image_fidelity: {name} is uint8 [N >= 1, 32, 32, 3]; got {_fidelity_kind(v)}")
+    for name, v in (("gray", gray), ("sse", sse), ("ssim", ssim), ("ssim_map", ssim_map)):
+        if not isinstance(v, bool):
+            raise ValueError(f"image_fidelity: {name} is a bool, got {v!r}")
+    for name, v in (("ia", ia), ("ib", ib)):
+        if v is not None and (not hasattr(v, "dtype") or str(v.dtype) not in ("torch.int32", "int32")
+                              or len(v.shape) != 1 or v.shape[0] < 1):
+            raise ValueError(f"image_fidelity: {name} is int32 [M >= 1]; got {_fidelity_kind(v)}")
+    if ia is not None and ib is not None and ia.shape[0] != ib.shape[0]:
+        raise ValueError(f"image_fidelity: ia has {ia.shape[0]} pairs, ib has {ib.shape[0]}")
+    Na, Nb = a.shape[0], b.shape[0]
+    if ia is not None:
+        M = ia.shape[0]
+    elif ib is not None:
+        M = ib.shape[0]
+    else:
+        if Na != Nb:
+            raise ValueError(f"image_fidelity: a has {Na} images, b has {Nb}, and neither ia nor ib says which are paired")
+        M = Na
+    if ia is None and M > Na:
+        raise ValueError(f"image_fidelity: ia is needed for {M} pairs out of the {Na} images of a")
+    if ib is None and M > Nb:
+        raise ValueError(f"image_fidelity: ib is needed for {M} pairs out of the {Nb} images of b")
+    mask_per_pair = 0
+    if mask is not None:
+        if not hasattr(mask, "dtype") or str(mask.dtype) not in ("torch.uint8", "uint8") \
+                or tuple(mask.shape) not in ((32, 32), (M, 32, 32)):
+            raise ValueError(f"image_fidelity: mask is uint8 [32, 32] or [{M}, 32, 32]; got {_fidelity_kind(mask)}")
+        mask_per_pair = int(len(mask.shape) == 3)
+    if not (sse or ssim or ssim_map or mask is not None):
+        raise ValueError("image_fidelity: nothing asked for (sse, ssim and ssim_map are off and there is no mask)")
+    return M, (1 if gray else 3), mask_per_pair
+
+
+def image_fidelity(a, b, *, ia=None, ib=None, gray=False, mask=None, sse=True, ssim=True, ssim_map=False):
+    """(sse | None, sse_masked | None, ssim | None, ssim_map | None) of M pairs of uint8 images, a [Na, 32, 32, 3] against
+    b [Nb, 32, 32, 3], on the device (mulan_image_fidelity).  Pair m is (a[ia[m]], b[ib[m]]), int32 [M] on the device, or
+    (a[m], b[m]) where the index tensor is None.  sse: int32 [M, 3], the exact sum of squared differences per channel;
+    sse_masked (returned with a mask: uint8 [32, 32] for all pairs or [M, 32, 32]): the same over the pixels whose
+    mask byte is not 0.  ssim: fp32 [M, P], the mean SSIM (Wang et al. 2004: 11 x 11 Gaussian of sigma 1.5, biased moments,
+    data range 255) over the 22 x 22 windows inside the image, per channel, or of the luma (SPECTRUM_GRAY) with gray:
+    P = 1.  ssim_map: fp32 [M, 22, 22, P], the per-window values.  An index out of range is not read: that pair's sums
+    are -1 and its SSIM NaN.  One fixed order per sum: the same call gives the same bits."""
+    M, P, per_pair = image_fidelity_check(a, b, ia, ib, gray, mask, sse, ssim, ssim_map)
+    tensors = [("a", a), ("b", b), ("ia", ia), ("ib", ib), ("mask", mask)]
+    if not torch.is_tensor(a) or any(v is not None and (not torch.is_tensor(v) or v.device != a.device) for _, v in tensors):
+        raise ValueError("image_fidelity: a, b, ia, ib and mask are tensors on one device")
+    dev = a.device
+    a, b, ia, ib, mask = _c(a), _c(b), _c(ia), _c(ib), _c(mask)
+    W = FIDELITY_WINDOWS
+    sse_out = torch.empty((M, 3), device=dev, dtype=torch.int32) if sse else None
+    masked_out = torch.empty((M, 3), device=dev, dtype=torch.int32) if mask is not None else None
+    ssim_out = torch.empty((M, P), device=dev, dtype=torch.float32) if ssim else None
+    map_out = torch.empty((M, W, W, P), device=dev, dtype=torch.float32) if ssim_map else None
+    call("mulan_image_fidelity", ptr(a), a.shape[0], ptr(b), b.shape[0], ptr(ia), ptr(ib), M, int(gray), ptr(mask),
+         per_pair, ptr(sse_out), ptr(masked_out), ptr(ssim_out), ptr(map_out), stream())
+    return sse_out, masked_out, ssim_out, map_out
+
+
+TSNE_MIN_N, TSNE_MAX_N = 4, 16384     # the range of mulan_tsne_*: P is dense, 1 GiB at the cap
 
 
 def _tsne_number(name, v, lo=None, lo_open=False, hi=None):
