@@ -640,6 +640,24 @@ size_t mulan_knn_u8_workspace(int Q, int k, int splits);
 int mulan_knn_u8(const unsigned char* q, const unsigned char* r, int Q, int N, int D, int k, int idx_base,
                  int self_offset, int accumulate, int splits, const int* radius2, unsigned char* covered, int* dist2,
                  int* idx, void* workspace, mulan_stream_t stream);
+/* Exact first and second moments of a set of uint8 rows, on the int8 matrix cores (moments.hip): for x [N][D], row-major
+ * and contiguous, and c = x - 128 as int8,
+ *   sum [D]       sum[j] = sum_i c[i][j]
+ *   gram [D][D]   gram[j][k] = sum_i c[i][j] c[i][k], written whole: only the 128 x 128 tiles on and above the diagonal
+ *                 are computed and the mirror is stored from the same totals, so gram equals its transpose bit for bit.
+ * Both are exact int64 and functions of the inputs alone (not of splits, the device or the schedule; no atomics).
+ *   accumulate    1: sum / gram are in/out, and this call's rows are added to what they hold (a set walked in chunks
+ *                 gives what one call over the whole set gives).  0: they are outputs.
+ *   splits        0: the library cuts the rows into slices so that the grid fills the device; > 0: that many (at most
+ *                 4096; slices beyond the 64-row chunks are empty).  The answer does not depend on it.
+ *   workspace     mulan_set_moments_u8_workspace(N, D, splits) bytes (0 for arguments that are refused), 8-byte aligned:
+ *                 the slices' int64 tiles and column sums, which a second launch adds up.
+ * x must be 16-byte aligned, sum, gram and workspace 8-byte.
+ * hipErrorInvalidValue, before anything is launched, for D not a multiple of 64 in [64, 4096], N < 1 or N > 2^24,
+ * accumulate outside 0..1, splits outside 0..4096, a NULL x / sum / gram / workspace, a misaligned pointer. */
+size_t mulan_set_moments_u8_workspace(int N, int D, int splits);
+int mulan_set_moments_u8(const unsigned char* x, int N, int D, int accumulate, int splits, long long* sum,
+                         long long* gram, void* workspace, mulan_stream_t stream);
 /* Spatial spectra of N images of 32 x 32 x 3, channels innermost (spectrum.hip): per image and plane the orthonormal
  * 2-D DCT-II Y = D X D^T, D[u][y] = c_u cos(pi (2 y + 1) u / 64), c_0 = sqrt(1 / 32), c_u = sqrt(2 / 32) otherwise -- what
  * scipy.fft.dctn(x, norm='ortho') gives -- on the fp32 matrix cores.  u is the vertical frequency, v the horizontal one.

@@ -98,6 +98,8 @@ SIGNATURES = {
     "mulan_bound_profile": [I, P, P, P, P, P, I, P, P, P, P, P, P, P, I, I, I, P],
     "mulan_knn_u8_workspace": [I, I, I],
     "mulan_knn_u8": [P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P],
+    "mulan_set_moments_u8_workspace": [I, I, I],
+    "mulan_set_moments_u8": [P, I, I, I, I, P, P, P, P],
     "mulan_spectrum_workspace": [I, I, I],
     "mulan_spectrum": [P, I, F, F, I, I, P, P, P, P, I, I, P, Z, P],
     "mulan_image_fidelity": [P, I, P, I, P, P, I, I, P, I, P, P, P, P, P],
@@ -150,7 +152,7 @@ SIGNATURES = {
     "mulan_stream_wait_signal": [P, P, ctypes.c_uint],
     "mulan_signal_read": [P, P],
 }
-_RESTYPES = {"mulan_rk_workspace_bytes": c_size_t, "mulan_bound_profile_workspace": c_size_t, "mulan_knn_u8_workspace": c_size_t, "mulan_spectrum_workspace": c_size_t, "mulan_tsne_workspace": c_size_t,"mulan_global_norm_clip_workspace": c_size_t, "mulan_conv3x3_wgrad_workspace": c_size_t, "mulan_conv3x3_pack_f16x3_bytes": c_size_t, "mulan_conv3x3_planes_bytes": c_size_t, "mulan_linear_pack_f16x3_bytes": c_size_t,
+_RESTYPES = {"mulan_rk_workspace_bytes": c_size_t, "mulan_bound_profile_workspace": c_size_t, "mulan_knn_u8_workspace": c_size_t, "mulan_set_moments_u8_workspace": c_size_t, "mulan_spectrum_workspace": c_size_t, "mulan_tsne_workspace": c_size_t,"mulan_global_norm_clip_workspace": c_size_t, "mulan_conv3x3_wgrad_workspace": c_size_t, "mulan_conv3x3_pack_f16x3_bytes": c_size_t, "mulan_conv3x3_planes_bytes": c_size_t, "mulan_linear_pack_f16x3_bytes": c_size_t,
              "mulan_linear_wgrad_f16x3_planes_workspace": c_size_t, "mulan_linear_wgrad_f16x3_x32_workspace": c_size_t,
              "mulan_conv3x3_wgrad_f16x3_planes_workspace": c_size_t, "mulan_conv3x3_wgrad_f16x3_workspace": c_size_t, "mulan_gemm_workspace": c_size_t, "mulan_version": c_char_p}
 

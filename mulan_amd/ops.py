@@ -2438,6 +2438,53 @@ def knn_u8(q, r, k, idx_base=0, self_offset=-1, out=None, radius2=None, covered=
     return (dist2, idx) if radius2 is None else (dist2, idx, covered)
 
 
+MOMENTS_MAX_D = 4096               # mulan_set_moments_u8: D a multiple of 64 in [64, 4096], at most 2^24 rows per call
+MOMENTS_MAX_N = 2 ** 24
+
+
+def set_moments_check(x, out=None, splits=0):
+    """every check of set_moments_u8 that needs no library call; x: anything with dtype and shape -> (N, D)"""
+    if not hasattr(x, "dtype") or str(x.dtype) not in ("torch.uint8", "uint8") or len(x.shape) != 2 or x.shape[0] < 1:
+        raise ValueError(f"set_moments_u8: x is uint8 [N >= 1, D]; got "
+                         f"{(x.dtype, tuple(x.shape)) if hasattr(x, 'dtype') else type(x).__name__}")
+    N, D = x.shape
+    if D % 64 or not 64 <= D <= MOMENTS_MAX_D:
+        raise ValueError(f"set_moments_u8: D is a multiple of 64 in [64, {MOMENTS_MAX_D}], got {D}")
+    if N > MOMENTS_MAX_N:
+        raise ValueError(f"set_moments_u8: at most 2^24 rows per call (accumulate with out=), got {N}")
+    if torch.is_tensor(x) and not x.is_contiguous():
+        raise ValueError("set_moments_u8: x is contiguous")
+    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits <= 4096:
+        raise ValueError(f"set_moments_u8: splits is 0 (the library chooses) or in [1, 4096], got {splits!r}")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("set_moments_u8: out is the pair (sum, gram) of an earlier call")
+        for name, v, shape in (("sum", out[0], (D,)), ("gram", out[1], (D, D))):
+            if not torch.is_tensor(v) or v.dtype != torch.int64 or tuple(v.shape) != shape or not v.is_contiguous():
+                raise ValueError(f"set_moments_u8: out's {name} is a contiguous int64 {list(shape)}")
+    return N, D
+
+
+def set_moments_u8(x, out=None, splits=0):
+    """(sum, gram), int64 [D] and [D, D] on x's device: the exact moments of the rows of x (uint8 [N, D]) about 128,
+    sum[j] = sum_i c[i, j] and gram[j, k] = sum_i c[i, j] c[i, k] with c = x - 128, from the int8 matrix cores
+    (mulan_set_moments_u8).  gram is written whole and equals its transpose bit for bit.  out = (sum, gram) of earlier
+    calls: this call's rows are added to them, in place (a set walked in chunks).  splits: slices of the rows, 0 for the
+    library's choice; the result does not depend on it."""
+    N, D = set_moments_check(x, out, splits)
+    if not torch.is_tensor(x):
+        raise ValueError("set_moments_u8: x is a tensor on the device")
+    dev = x.device
+    if out is not None and any(v.device != dev for v in out):
+        raise ValueError(f"set_moments_u8: out is on {[str(v.device) for v in out]}, x on {dev}")
+    accumulate = out is not None
+    total, gram = out if accumulate else (torch.empty(D, device=dev, dtype=torch.int64),
+                                          torch.empty((D, D), device=dev, dtype=torch.int64))
+    ws = torch.empty(lib.load().mulan_set_moments_u8_workspace(N, D, int(splits)) // 8, device=dev, dtype=torch.int64)
+    call("mulan_set_moments_u8", ptr(x), N, D, int(accumulate), int(splits), ptr(total), ptr(gram), ptr(ws), stream())
+    return total, gram
+
+
 SPECTRUM_BINS = 45                 # radial bins of a 32 x 32 DCT: floor(sqrt(u^2 + v^2) + 1/2) = 0 .. 44
 SPECTRUM_GRAY = (0.2125, 0.7154, 0.0721)   # skimage.color.rgb2gray; the kernel holds the same constants
 
