@@ -399,7 +399,8 @@ int mulan_softmax_scaled_bwd(const float* p, const float* dp, float* ds, size_t 
 int mulan_fourier_fwd(const float* z, float* out, size_t npix, mulan_stream_t stream);
 int mulan_fourier_bwd(const float* z, const float* dout, float* dz, size_t npix, int accumulate,
                       mulan_stream_t stream);
-/* get_timestep_embedding (model_vdm.py:391-413): out[r][col0 .. col0+E) = [sin, cos](1000 t_r w_k) */
+/* get_timestep_embedding (model_vdm.py:391-413): out[r][col0 .. col0+E) = [sin, cos](1000 t_r w_k); E even and >= 4,
+ * 0 <= col0 and col0 + E <= ld (a row that ran past ld would land in the next one) */
 int mulan_temb_fwd(const float* t, float* out, int n, int E, int ld, int col0, mulan_stream_t stream);
 int mulan_temb_bwd(const float* t, const float* dout, float* dt, int n, int E, int ld, int col0,
                    mulan_stream_t stream);

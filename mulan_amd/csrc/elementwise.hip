@@ -335,13 +335,13 @@ MULAN_API int mulan_fourier_bwd(const float* z, const float* dout, float* dz, si
   MULAN_CHECK_LAUNCH();
 }
 MULAN_API int mulan_temb_fwd(const float* t, float* out, int n, int E, int ld, int col0, hipStream_t stream) {
-  if (E < 4 || (E & 1)) return (int)hipErrorInvalidValue;
+  if (E < 4 || (E & 1) || col0 < 0 || ld < col0 + E) return (int)hipErrorInvalidValue;   // rows would overlap
   hipLaunchKernelGGL(temb_fwd_kernel, dim3(nblocks((size_t)n * (E / 2))), dim3(256), 0, stream, t, out, n, E, ld, col0);
   MULAN_CHECK_LAUNCH();
 }
 MULAN_API int mulan_temb_bwd(const float* t, const float* dout, float* dt, int n, int E, int ld, int col0,
                              hipStream_t stream) {
-  if (E < 4 || (E & 1)) return (int)hipErrorInvalidValue;
+  if (E < 4 || (E & 1) || col0 < 0 || ld < col0 + E) return (int)hipErrorInvalidValue;   // rows would overlap
   hipLaunchKernelGGL(temb_bwd_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, t, dout, dt, n, E, ld, col0);
   MULAN_CHECK_LAUNCH();
 }
